@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the ADMM hot path on MI355X.
 
-    python bench.py --gpus 1 --steps 50 --warmup 2
+    python bench.py --gpus 1 --steps 50 --warmup 2 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,13 +12,22 @@ final unpack / gather, bracketed by barrier + torch.cuda.synchronize(); the time
 With N > 1 the only exchange of the path -- the gather of the x shards to rank 0 -- is inside the timed region; with
 --gather-chunks c a rank solves its block as c sub-blocks and the asynchronous gather of one overlaps the solve of the next.
 
+A plain run sets up, warms up (a W-iteration solve, then an untimed K-iteration solve that allocates what depends on the
+iteration count), times the K-iteration solve and prints the line: no per-kernel events in the timed region, no extra legs.
+Everything else described below (`roofline`, the cfg3 / cfg4 legs, `cpu_baseline`) runs only with --full; --no-prof,
+--no-cfg3-leg, --no-cfg4-leg and --no-cpu-baseline switch its parts off.
+--dump-outputs DIR writes the solution x (samples, T, N, C) of the timed solve as DIR/x.npy (float32): all samples of the
+global batch when they fit in 48 MiB, otherwise a fixed sample of whole windows (seed 0, ascending global index); the
+line then carries `dumped_outputs` (shape and dtype of what was written).
+The inputs depend only on the arguments (seeded graph and signals), so two builds can be compared output for output.
+
 Workloads (BASELINE.json configs; synthetic data, seeds fixed):
   cfg2 (default) PEMS04-shaped graph: N=307, 340 undirected edges, k=4, B=4096 windows per GPU, fp32
   cfg3           N=10 000 Euclidean kNN graph, B=512 per GPU, fp32     (CG-SpMV HBM roofline run)
   cfg4           N=100 000 mixed graph, B=256 per GPU (weak scaling 1..8 GPUs), fp32
 Metric: ADMM sample-iterations per second = (samples over all ranks) * K / seconds.
 
-Rank 0 prints ONE JSON line.  `roofline` describes the dominant kernel of the timed workload, measured live with
+Rank 0 prints ONE JSON line.  `roofline` (--full) describes the dominant kernel of the timed workload, measured live with
 HIP events recorded around every launch on the launch stream during the timed solve:
   * cfg2 (LDS-resident path): k_admm_lds never streams its vectors from HBM, so it is priced against the LDS:
     `bound` = "lds", `achieved` = LDS bytes the kernel's gathers / stores move per launch (exact count from the table
@@ -28,11 +37,11 @@ HIP events recorded around every launch on the launch stream during the timed so
     iteration), `hbm_achieved` = traffic / duration.
   * cfg3 / cfg4 (streaming path): the sparse-Laplacian SpMM inside the CG solves against the HBM roofline
     (`bound` = "hbm", 8 TB/s), algorithmic bytes per launch as accumulated by the library.
-The default (cfg2) run also measures the cfg3 SpMM roofline -- the configuration the >= 60 % target is quoted on -- over
+With --full the default (cfg2) run also measures the cfg3 SpMM roofline -- the configuration the >= 60 % target is quoted on -- over
 6 ADMM iterations (> 200 live launches); its figures are flattened into the same `roofline` object as `cfg3_spmm_*`, and a
 2-iteration leg on the 100k-node graph of cfg4 (B = 256, the per-GPU slice) is reported as `roofline_cfg4`.
 `device_state` (and `roofline_cfg3/4.device_state`; only with --device-state): engine / memory clock and board power from sysfs.
-`cpu_baseline` is the CPU oracle (NumPy/SciPy restatement of the reference) on a bounded sample of the same windows:
+`cpu_baseline` (--full) is the CPU oracle (NumPy/SciPy restatement of the reference) on a bounded sample of the same windows:
 one worker process per host core (at most 16, the GPU box's CPU share), each solving its windows one at a time
 (B = 1: the reference's semantics), plus the vectorised-batch rate of one core and the full cfg1 run.
 """
@@ -55,6 +64,7 @@ import torch.distributed as dist  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0    # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy ceiling
 LDS_PEAK_GBS = 150000.0  # aggregate ds_read_b64/b128 rate with every CU streaming (MI355X_MICROARCH.md, LDS section)
+DUMP_BYTES = 48 << 20    # cap of --dump-outputs (cfg2: 1 707 of the 4 096 windows of 29.5 KB)
 
 
 def pems_like_graph(n, n_edges, seed=0):
@@ -226,6 +236,19 @@ def make_solver(n, cl, dl, info, device):
     return blk
 
 
+def dump_outputs(out_dir, x):
+    """x (global batch, T, N, C) of the timed solve -> out_dir/x.npy; returns what was written (see the module docstring)."""
+    assert x.dtype in (torch.float32, torch.float64), x.dtype
+    row = x[0].numel() * x.element_size()
+    nb = x.shape[0]
+    if nb * row > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(nb, DUMP_BYTES // row, replace=False))
+        x = x.index_select(0, torch.from_numpy(idx).to(x.device))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "x.npy"), x.cpu().numpy())
+    return {"x": {"shape": list(x.shape), "dtype": str(x.dtype).replace("torch.", ""), "of_samples": nb}}
+
+
 def _oracle_inputs(cl, blk, info, y_dev, path):
     np.savez(path, cl=cl.numpy(), u_ew=blk.u_ew[0].numpy(), d_ew=blk.d_ew[0].numpy(), y=y_dev.double().cpu().numpy(),
              t_in=12, T=24, **{k: float(v) for k, v in info.items()})
@@ -380,14 +403,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="cfg2", choices=["cfg2", "cfg3", "cfg4"])
     ap.add_argument("--batch", type=int, default=0, help="override the per-GPU batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cfg3-leg", action="store_true", help="skip the streaming-path legs (cfg3 and cfg4)")
-    ap.add_argument("--no-cfg4-leg", action="store_true", help="skip the 100k-node leg only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write x of the timed solve to DIR/x.npy (see the module docstring)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the per-kernel roofline (HIP events in the timed region), the cfg3 / cfg4 legs and the CPU "
+                         "baseline; off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-cfg3-leg", action="store_true", help="with --full: skip the streaming-path legs (cfg3 and cfg4)")
+    ap.add_argument("--no-cfg4-leg", action="store_true", help="with --full: skip the 100k-node leg only")
     ap.add_argument("--device-state", action="store_true",
                     help="report engine / memory clock and board power from sysfs as `device_state` (off by default: a run that "
                          "merely looks the card up in sysfs before the timed region measured 4-5 %% slower on cfg2 -- 1 766 vs "
                          "1 845 us per iteration of k_admm_lds, alternating runs on three boxes; the reads themselves come after)")
-    ap.add_argument("--no-prof", action="store_true", help="do not record per-kernel HIP events in the timed region")
+    ap.add_argument("--no-prof", action="store_true", help="with --full: do not record per-kernel HIP events in the timed region")
     ap.add_argument("--cpu-budget", type=float, default=30.0)
     ap.add_argument("--gather-chunks", type=int, default=1,
                     help="N > 1: sub-blocks per rank; the final gather of one overlaps the solve of the next "
@@ -395,6 +422,9 @@ def main():
                          "sample-iterations/s, fixed per-solve work -- which is more than the overlap hides of a 120 MB/rank "
                          "gather; the streaming workloads would also drop to a narrower vector width)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    prof_on = args.full and not args.no_prof
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -453,25 +483,25 @@ def main():
         for _, _, work in pending:
             if work is not None:
                 work.wait()
-        return x, None
+        return x, pending
 
     # warm-up (untimed): creates the solver workspace and the HIP event pool, pages kernels in
     run(max(1, args.warmup), False)
-    run(args.steps, not args.no_prof)       # a solve of the timed length allocates whatever depends on the iteration count (iterate
-    if not args.no_prof:                    # buffers of the chunked schedule); the event pool of mgadmm_prof_begin is created on first use
+    run(args.steps, prof_on)                # a solve of the timed length allocates whatever depends on the iteration count (iterate
+    if prof_on:                             # buffers of the chunked schedule); the event pool of mgadmm_prof_begin is created on first use
         blk.prof_end()
     sampler = DeviceSampler(DeviceSampler.pci_address(local), period=None) if rank == 0 and args.device_state else None
     barrier()
     t0 = time.perf_counter()
-    x, prof = run(args.steps, not args.no_prof)
+    x, pending = run(args.steps, prof_on)
     barrier()
     dt = time.perf_counter() - t0
     if sampler is not None:
         sampler.read_once()          # clocks / averaged power right after the timed region (never during it: see DeviceSampler)
     # the HIP events were recorded around every launch INSIDE the timed region; their elapsed times are read after it
     t1 = time.perf_counter()
-    prof = blk.prof_end() if not args.no_prof else None
-    prof_read_ms = (time.perf_counter() - t1) * 1e3 if not args.no_prof else 0.0
+    prof = blk.prof_end() if prof_on else None
+    prof_read_ms = (time.perf_counter() - t1) * 1e3 if prof_on else 0.0
     tmax = torch.tensor([dt], device=cdev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -496,12 +526,17 @@ def main():
                                       + (f" in {chunks} sub-blocks (all but the last overlap the next sub-block's solve)"
                                          if world > 1 else ""),
                        "mean_cg_iters": cg_counts, "solver_path": path, "all_finite": finite,
-                       "workspace_GB": blk.workspace_bytes() / 1e9, "per_kernel_events_in_timed_region": not args.no_prof,
+                       "workspace_GB": blk.workspace_bytes() / 1e9, "per_kernel_events_in_timed_region": prof_on,
                        "event_readback_ms_after_timed_region": round(prof_read_ms, 3)},
         }
         out["config"]["mean_cg_iters_x_zu_zd"] = [round(cg_counts[k2], 2) for k2 in ("CG_iter_x", "CG_iter_zu", "CG_iter_zd")]
         out["device_state"] = sampler.summary() if sampler is not None else None
         out["roofline"] = roofline_from_prof(prof, args.workload, path, blk=blk, B=Bc, cg=cg_counts, steps=args.steps * len(blocks)) if prof else None
+        if args.dump_outputs:
+            xall = x if world == 1 else torch.cat([g[r] for r in range(world) for _, g, _ in pending])
+            out["dumped_outputs"] = dump_outputs(args.dump_outputs, xall)
+            del xall
+    del pending
 
     # ---- CG-SpMV roofline legs on the streaming path, rank 0 of a 1-GPU run only: cfg3 (10k-node graph, BASELINE config 3:
     # the configuration the >= 60 % target is quoted on) and a short cfg4 leg (100k-node graph, the per-GPU slice of BASELINE
@@ -532,7 +567,7 @@ def main():
         torch.cuda.empty_cache()
         return r3
 
-    if rank == 0 and world == 1 and args.workload == "cfg2" and not args.no_cfg3_leg:
+    if args.full and rank == 0 and world == 1 and args.workload == "cfg2" and not args.no_cfg3_leg:
         blk.close()
         del x
         torch.cuda.empty_cache()
@@ -548,7 +583,7 @@ def main():
             except Exception as e:  # noqa: BLE001  (52 GB workspace: never lose the line to it)
                 out["roofline_cfg4"] = {"error": repr(e)}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             nb, Bb, clb, dlb, infob, _ = build_problem(args.workload)
             bb = make_solver(nb, clb, dlb, infob, device)

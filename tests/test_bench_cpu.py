@@ -31,3 +31,21 @@ def test_synthetic_inputs_are_deterministic():
     y2 = bench.synth_y(64, 5, 12, seed=1, offset=3, device=torch.device("cpu"))
     assert y1.shape == (5, 12, 64, 1) and torch.equal(y1, y2)
     assert not torch.equal(y1, bench.synth_y(64, 5, 12, seed=1, offset=4, device=torch.device("cpu")))
+
+
+def test_dump_outputs_writes_all_or_a_fixed_sample_of_windows(tmp_path, monkeypatch):
+    import bench
+    x = torch.arange(10 * 3 * 4, dtype=torch.float32).reshape(10, 3, 4, 1)
+    info = bench.dump_outputs(str(tmp_path / "all"), x)
+    np.testing.assert_array_equal(np.load(tmp_path / "all" / "x.npy"), x.numpy())
+    assert info["x"]["shape"] == [10, 3, 4, 1] and info["x"]["dtype"] == "float32"
+    row = 3 * 4 * 4
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * row + 5)              # room for 4 whole windows
+    bench.dump_outputs(str(tmp_path / "a"), x)
+    bench.dump_outputs(str(tmp_path / "b"), x)
+    a, b = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert a.shape == (4, 3, 4, 1) and a.dtype == np.float32
+    np.testing.assert_array_equal(a, b)                                 # the same windows every time
+    idx = (a[:, 0, 0, 0] // (3 * 4)).astype(int)                      # window i starts at element 12 i
+    assert list(idx) == sorted(set(idx)) and all(0 <= i < 10 for i in idx)
+    np.testing.assert_array_equal(a, x.numpy()[idx])

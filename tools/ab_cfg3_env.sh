@@ -3,7 +3,7 @@
 rounds=$1; var=$2; shift 2
 for r in $(seq 1 $rounds); do
   for v in "$@"; do
-    env $var=$v python bench.py --workload cfg3 --steps 6 --warmup 1 --no-cpu-baseline > /tmp/ab_bench.log 2>&1
+    env $var=$v python bench.py --full --workload cfg3 --steps 6 --warmup 1 --no-cpu-baseline > /tmp/ab_bench.log 2>&1
     python - "$var=$v" <<'P'
 import json, sys
 d = json.loads(open("/tmp/ab_bench.log").read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 rounds=$1; var=$2; shift 2
 for r in $(seq 1 $rounds); do
   for v in "$@"; do
-    env $var=$v python bench.py --no-cpu-baseline --no-cfg3-leg --warmup 5 > /tmp/ab_bench.log 2>&1
+    env $var=$v python bench.py --full --no-cpu-baseline --no-cfg3-leg --warmup 5 > /tmp/ab_bench.log 2>&1
     python - "$var=$v" <<'P'
 import json, sys
 d = json.loads(open("/tmp/ab_bench.log").read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@
 rounds=$1; shift
 for r in $(seq 1 $rounds); do
   for lib in "$@"; do
-    MGADMM_LIB=$PWD/$lib python bench.py --no-cpu-baseline --no-cfg3-leg --warmup 5 > /tmp/ab_bench.log 2>&1
+    MGADMM_LIB=$PWD/$lib python bench.py --full --no-cpu-baseline --no-cfg3-leg --warmup 5 > /tmp/ab_bench.log 2>&1
     python - "$lib" <<'P'
 import json, sys
 d = json.loads(open("/tmp/ab_bench.log").read().strip().splitlines()[-1])

@@ -1,6 +1,6 @@
 for r in 1 2 3; do
   for f in "" "--device-state"; do
-    python bench.py --no-cpu-baseline --no-cfg3-leg --warmup 5 $f > /tmp/ab_bench.log 2>&1
+    python bench.py --full --no-cpu-baseline --no-cfg3-leg --warmup 5 $f > /tmp/ab_bench.log 2>&1
     python - "flag=$f" <<'P'
 import json, sys
 d = json.loads(open("/tmp/ab_bench.log").read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # All rocprofv3 passes behind profiles/rNN/ in one GPU session (run from the repo root on the GPU box):
 #   tools/profile_round.sh <rNN>
 # kernel trace + stats, FETCH_SIZE pass, WRITE_SIZE pass (separate runs, as MI355X_MICROARCH.md prescribes), two SQ counter
-# passes, a MGADMM_FOLD=0 stats pass (SpMM-only rows) and a 5-launch cfg2 trace (timeline), each of `python3 bench.py --steps 7 --warmup 1 --no-cpu-baseline --no-cfg4-leg --no-prof` (7 steps = ONE k_admm_lds launch of 7 iterations) + the FETCH_SIZE calibration; summaries are written to
+# passes, a MGADMM_FOLD=0 stats pass (SpMM-only rows) and a 5-launch cfg2 trace (timeline), each of `python3 bench.py --full --steps 7 --warmup 1 --no-cpu-baseline --no-cfg4-leg --no-prof` (7 steps = ONE k_admm_lds launch of 7 iterations) + the FETCH_SIZE calibration; summaries are written to
 # gpurun_out/profiles_<rNN>/ (copy them into profiles/<rNN>/) and profiles/traffic.json is rewritten there too.
 set -u
 r=$1
@@ -10,7 +10,7 @@ out=$PWD/gpurun_out/profiles_$r
 mkdir -p $out/$r
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 W=/tmp/prof_$r; rm -rf $W; mkdir -p $W
-CMD="python3 bench.py --steps 7 --warmup 1 --no-cpu-baseline --no-cfg4-leg --no-prof"
+CMD="python3 bench.py --full --steps 7 --warmup 1 --no-cpu-baseline --no-cfg4-leg --no-prof"
 run() { name=$1; shift; echo "== $name"; rocprofv3 "$@" -d $W/$name -o p --output-format csv -- ${ALT:-$CMD} > $W/$name.log 2>&1 || { echo "pass $name failed"; tail -5 $W/$name.log; exit 1; }; }
 run stats --kernel-trace --stats
 MGADMM_FOLD=0 run fold0 --kernel-trace --stats

@@ -9,10 +9,10 @@ W=${1:-cfg4}; K=${2:-3}; WU=${3:-1}; NS=${4:-"1 2 4 8"}
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 for N in $NS; do
   if [ "$N" = 1 ]; then
-    python bench.py --gpus 1 --steps "$K" --warmup "$WU" --workload "$W" --no-cpu-baseline --no-cfg3-leg
+    python bench.py --gpus 1 --steps "$K" --warmup "$WU" --workload "$W" --full --no-cpu-baseline --no-cfg3-leg
   else
     PORT=$((29500 + RANDOM % 2000))
     python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port "$PORT" \
-      bench.py --gpus "$N" --steps "$K" --warmup "$WU" --workload "$W" --no-cpu-baseline --no-cfg3-leg
+      bench.py --gpus "$N" --steps "$K" --warmup "$WU" --workload "$W" --full --no-cpu-baseline --no-cfg3-leg
   fi || { echo "{\"n_gpus\": $N, \"error\": \"bench.py failed\"}"; exit 1; }
 done
