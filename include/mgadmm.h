@@ -178,7 +178,10 @@ typedef enum {
     MGADMM_Q_LDS_SLOTS = 12,    /* 1: two LDS vectors park per-thread operands across the solves                    */
     MGADMM_Q_LDS_CHUNK = 13,    /* ADMM iterations per k_admm_lds launch when the iteration count is fixed          */
     MGADMM_Q_LDS_ROWS = 14,     /* LDS rows of an image: nodes + ghost rows                                         */
-    MGADMM_Q_CLDR_SLOTS = 15    /* W_d^T entry slots per row of the fused Ldr^T Ldr kernel in use (12 / 16 / 24); 0: two-pass */
+    MGADMM_Q_CLDR_SLOTS = 15,   /* W_d^T entry slots per row of the fused Ldr^T Ldr kernel in use (12 / 16 / 24); 0: two-pass */
+    MGADMM_Q_LDS_INSTANCE = 16  /* template arguments <TPG, BAND, MAXT, SB, NU, ND, SLOTS, TP> of the k_admm_lds instance the
+                                   last LDS launch ran, packed: bits 0-7 TPG, 8 BAND, 9 SB, 10 SLOTS, 11-15 NU, 16-20 ND,
+                                   21-31 MAXT, 32-39 TP + 1; -1 before the first launch                                   */
 } mgadmm_query_t;
 int mgadmm_solver_query(const mgadmm_solver* s, int32_t what, int64_t* out);
 

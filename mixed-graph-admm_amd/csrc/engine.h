@@ -99,6 +99,7 @@ struct Engine : EngineBase {
     int* d_stop = nullptr;
     double* d_ps_ring = nullptr;  // [LDS_SETS][J][NMETRIC][Bp]: per-sample metric sums of the chunked schedule
     std::vector<float*> lds_ring_extra;   // iterate buffers beyond the 15 workspace vectors (chunks longer than 7 iterations)
+    int64_t lds_instance = -1;       // MGADMM_Q_LDS_INSTANCE: template arguments of the k_admm_lds instance of the last launch
     int lds_chunk = LDS_MAXJ_POOL;   // MGADMM_LDS_CHUNK: ADMM iterations per k_admm_lds launch when the iteration count is fixed (1 .. LDS_MAXJ_POOL)
     hipStream_t st_side = nullptr;
     hipEvent_t ev_main[LDS_NBOUND] = {nullptr}, ev_side[LDS_NBOUND] = {nullptr};
@@ -530,6 +531,7 @@ struct Engine : EngineBase {
             case MGADMM_Q_LDS_CHUNK: *out = std::max(1, std::min(lds_chunk, LDS_MAXJ_POOL)); break;
             case MGADMM_Q_LDS_ROWS: *out = lds.NR; break;
             case MGADMM_Q_CLDR_SLOTS: *out = cldr_dev.state == 1 ? cl_gt : 0; break;      // (prepared by the first operator application)
+            case MGADMM_Q_LDS_INSTANCE: *out = lds_instance; break;
             case MGADMM_Q_NNZ_U: *out = g->hWu.nnz(); break;
             case MGADMM_Q_NNZ_D: *out = g->hWd.nnz(); break;
             case MGADMM_Q_NNZ_DT: *out = g->hWdT.nnz(); break;
@@ -1585,7 +1587,7 @@ struct Engine : EngineBase {
 
     int launch_lds(const LdsArgs& a, int B) {
         const bool timed = prof_open(0, 0.0);
-        LdsLaunch L{lds.TPG, lds.maxt, lds.sb, lds.uniform45, lds.slots, lds.block, lds.lds_bytes};
+        LdsLaunch L{lds.TPG, lds.maxt, lds.sb, lds.uniform45, lds.slots, lds.block, lds.lds_bytes, &lds_instance};
         const int rc = mg_lds_iteration(L, a, B, st);
         if (timed) prof_close();
         return rc;

@@ -61,6 +61,7 @@ struct LdsLaunch {
     int slots;      // uniform45 only: two more LDS vectors hold per-thread operands across the solves of an iteration
     int block;      // threads per workgroup
     size_t lds_bytes;
+    int64_t* instance;  // receives the packed template arguments of the instance launched (MGADMM_Q_LDS_INSTANCE), or nullptr
 };
 
 // J ADMM iterations for B samples (one workgroup per sample); returns a mgadmm_status

@@ -28,6 +28,9 @@ int launch(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t st) {
     MG_TRY(allow_lds((const void*)fn, 160 * 1024));
     hipLaunchKernelGGL(fn, dim3(B), dim3(L.block), L.lds_bytes, st, a);
     MG_HIP(hipGetLastError());
+    if (L.instance)         // which of the instances below ran (tests: the instance census)
+        *L.instance = TPG | (int64_t)BAND << 8 | (int64_t)SB << 9 | (int64_t)SLOTS << 10 | (int64_t)NU << 11 | (int64_t)ND << 16 |
+                      (int64_t)MAXT << 21 | (int64_t)(TP + 1) << 32;
     return MGADMM_OK;
 }
 

@@ -28,7 +28,7 @@ NMETRIC = 11
  M_RECOVER) = range(11)
 NPROF = 4
 (Q_LDS_OK, Q_LDS_TPG, Q_LDS_THREADS, Q_LDS_BYTES, Q_LDS_ROW_STRIDE, Q_NNZ_U, Q_NNZ_D, Q_NNZ_DT, Q_TILE_ROWS, Q_LDS_UNIFORM,
- Q_LDS_TAIL_PAIRS, Q_LDS_LEAD, Q_LDS_SLOTS, Q_LDS_CHUNK, Q_LDS_ROWS, Q_CLDR_SLOTS) = range(16)
+ Q_LDS_TAIL_PAIRS, Q_LDS_LEAD, Q_LDS_SLOTS, Q_LDS_CHUNK, Q_LDS_ROWS, Q_CLDR_SLOTS, Q_LDS_INSTANCE) = range(17)
 
 _i32p = C.POINTER(C.c_int32)
 _f32p = C.POINTER(C.c_float)
@@ -143,3 +143,18 @@ def query(handle, what):
     out = C.c_int64()
     check(lib.mgadmm_solver_query(handle, what, C.byref(out)))
     return int(out.value)
+
+
+def decode_lds_instance(v):
+    """Packed MGADMM_Q_LDS_INSTANCE value -> the instance name as `nm -C` prints it, e.g.
+    'k_admm_lds<12, false, 640, false, 4, 5, true, 2>'; None for -1 (no launch yet)."""
+    if v < 0:
+        return None
+    b = lambda bit: "true" if (v >> bit) & 1 else "false"
+    args = [v & 0xFF, b(8), (v >> 21) & 0x7FF, b(9), (v >> 11) & 0x1F, (v >> 16) & 0x1F, b(10), ((v >> 32) & 0xFF) - 1]
+    return "k_admm_lds<" + ", ".join(str(a) for a in args) + ">"
+
+
+def lds_instance(handle):
+    """Name of the k_admm_lds instance the solver's last LDS launch ran (None before the first launch)."""
+    return decode_lds_instance(query(handle, Q_LDS_INSTANCE))

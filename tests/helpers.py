@@ -72,3 +72,66 @@ def case_inputs(meta, task, np_dtype):
         return meta["x_true"][:, :t_in].astype(np_dtype), None
     mask = meta["mask"]
     return (meta["x_true"] * mask).astype(np_dtype), mask
+
+
+F32_EPS = 2.0 ** -23
+
+
+def finite_termination(h, nm, n_it):
+    """(iters, windows) bool: the oracle's CG solve ended with a step that cut ||r|| by more than float32 resolves
+    (||r_k|| / ||r_k-1|| = sqrt(beta_k) < 2^-23) -- exact termination on a system with few distinct eigenvalues, not
+    convergence.  The float32 residual of that step is rounding only."""
+    w = nm.replace("CG_iter", "beta")
+    its = np.array(getattr(h, nm)).reshape(n_it, -1)
+    out = np.zeros(its.shape, dtype=bool)
+    for i, be in enumerate(getattr(h, w)):
+        for j in range(its.shape[1]):
+            k = its[i, j]
+            out[i, j] = k > 0 and np.sqrt(be[k - 1, j]) < F32_EPS
+    return out
+
+
+def check_windows(tag, blk, x, idx, o, xo, xtol=1e-5, htol=1e-3, slack=1, abl="None", finite_termination_rule=False):
+    """GPU batch result `x` (+ blk.metrics_per_sample, blk.CG_iter_*) against the oracle run on windows `idx`.
+    Tolerances of the BASELINE configs (float32 kernels vs the float64 oracle): x per sample, every history list, CG counts
+    (the diagonal x solve of 'DGTV' / 'UT' gets the +-2 of check_solve in test_gpu_parity.py).
+    finite_termination_rule: a solve whose float64 count is a finite-termination count (finite_termination) may also lie
+    in [ref - 1, 2 ref + 1], the bound test_gpu_random.py sets for such counts: float32 loses the exact termination and
+    runs on until its recursive residual passes the tolerance."""
+    from mgadmm import _lib as L
+    has_phi, has_zd = abl in ("None", "DGLR"), abl != "DGLR"
+    idx = np.asarray(idx)
+    xg = x[torch.as_tensor(idx, device=x.device)].double().cpu().numpy()
+    err = np.linalg.norm((xg - xo).reshape(len(idx), -1), axis=1) / np.linalg.norm(xo.reshape(len(idx), -1), axis=1)
+    assert err.max() < xtol, (tag, "x", err.max())
+    mps = blk.metrics_per_sample[:, :, idx]                  # (iters, NMETRIC, k) per-sample sums
+    h = o.hist
+    n_it = len(h.p_res_list)
+    assert mps.shape[0] == n_it
+    # norms of DIFFERENCES of float32 vectors (||x - x_old||, ||z - z_old||, ...) carry the rounding of the vectors
+    # themselves: 2 ulp of float32 relative to ||x_ref|| is the resolution (cfg4, iteration 0: ||x1 - x0|| = 1.4 on
+    # ||x|| = 5.4e5 -- the initial guess almost solves the first x-update -- measured difference 0.03 = 6e-8 ||x||)
+    floor = 1e-7 * float(np.linalg.norm(xo))
+    norm = lambda m: np.sqrt(mps[:, m].sum(1))
+    mean = lambda m: mps[:, m].mean(1)
+    res = [(L.M_PRI_ZU, L.M_DUAL_ZU)] + [(L.M_PRI_PHI, L.M_DUAL_PHI)] * has_phi + [(L.M_PRI_ZD, L.M_DUAL_ZD)] * has_zd
+    pri = np.stack([norm(p) for p, _ in res], 1)
+    dual = np.stack([norm(d) for _, d in res], 1)
+    np.testing.assert_allclose(pri, np.array(h.p_res_list), rtol=htol, atol=floor, err_msg=f"{tag} primal residuals")
+    np.testing.assert_allclose(dual, np.array(h.d_res_list), rtol=htol, atol=floor, err_msg=f"{tag} dual residuals")
+    np.testing.assert_allclose(norm(L.M_XSHIFT), np.array(h.x_shift_list), rtol=htol, atol=floor, err_msg=f"{tag} x shift")
+    np.testing.assert_allclose(norm(L.M_RECOVER), np.array(h.recover_list), rtol=htol, atol=floor, err_msg=f"{tag} ||Hx-y||")
+    np.testing.assert_allclose(mean(L.M_GLR), np.array(h.GLR_list), rtol=htol, err_msg=f"{tag} GLR")
+    if has_phi:
+        np.testing.assert_allclose(mean(L.M_DGTV), np.array(h.DGTV_list), rtol=htol, err_msg=f"{tag} DGTV")
+    if has_zd:
+        np.testing.assert_allclose(mean(L.M_DGLR), np.array(h.DGLR_list), rtol=htol, err_msg=f"{tag} DGLR")
+    for nm in ("CG_iter_x", "CG_iter_zu") + ("CG_iter_zd",) * has_zd:
+        got = torch.stack(getattr(blk, nm)).numpy()[:, idx]
+        ref = np.array(getattr(h, nm)).reshape(n_it, -1)
+        s = slack if nm != "CG_iter_x" or has_phi else max(slack, 2)
+        assert (got > 0).all(), (tag, nm, "CG did not converge")
+        ok = np.abs(got - ref) <= s
+        if finite_termination_rule and s == slack:         # (the diagonal x solves keep their own slack)
+            ok |= finite_termination(h, nm, n_it) & (got >= ref - 1) & (got <= 2 * ref + 1)
+        assert ok.all(), (tag, nm, np.abs(got - ref).max())

@@ -24,11 +24,10 @@ import pytest
 import torch
 
 from conftest import ROOT
+from helpers import check_windows as _check_windows
 
 sys.path.insert(0, ROOT)
 pytestmark = pytest.mark.gpu
-
-X_TOL, HIST_RTOL, CG_SLACK = 1e-5, 1e-3, 1
 
 
 def _bench():
@@ -48,39 +47,6 @@ def _problem(workload, **kw):
 def _oracle(blk, cl, info):
     from oracle import admm_oracle as orc
     return orc.OracleADMM(cl.numpy(), blk.u_ew[0].numpy(), blk.d_ew[0].numpy(), info, mode="knn", t_in=12, T=24)
-
-
-def _check_windows(tag, blk, x, idx, o, xo, xtol=X_TOL, htol=HIST_RTOL, slack=CG_SLACK):
-    """GPU batch result `x` (+ blk.metrics_per_sample, blk.CG_iter_*) against the oracle run on windows `idx`."""
-    from mgadmm import _lib as L
-    idx = np.asarray(idx)
-    xg = x[torch.as_tensor(idx, device=x.device)].double().cpu().numpy()
-    err = np.linalg.norm((xg - xo).reshape(len(idx), -1), axis=1) / np.linalg.norm(xo.reshape(len(idx), -1), axis=1)
-    assert err.max() < xtol, (tag, "x", err.max())
-    mps = blk.metrics_per_sample[:, :, idx]                  # (iters, NMETRIC, k) per-sample sums
-    h = o.hist
-    n_it = len(h.p_res_list)
-    assert mps.shape[0] == n_it
-    # norms of DIFFERENCES of float32 vectors (||x - x_old||, ||z - z_old||, ...) carry the rounding of the vectors
-    # themselves: 2 ulp of float32 relative to ||x_ref|| is the resolution (cfg4, iteration 0: ||x1 - x0|| = 1.4 on
-    # ||x|| = 5.4e5 -- the initial guess almost solves the first x-update -- measured difference 0.03 = 6e-8 ||x||)
-    floor = 1e-7 * float(np.linalg.norm(xo))
-    norm = lambda m: np.sqrt(mps[:, m].sum(1))
-    mean = lambda m: mps[:, m].mean(1)
-    pri = np.stack([norm(L.M_PRI_ZU), norm(L.M_PRI_PHI), norm(L.M_PRI_ZD)], 1)
-    dual = np.stack([norm(L.M_DUAL_ZU), norm(L.M_DUAL_PHI), norm(L.M_DUAL_ZD)], 1)
-    np.testing.assert_allclose(pri, np.array(h.p_res_list), rtol=htol, atol=floor, err_msg=f"{tag} primal residuals")
-    np.testing.assert_allclose(dual, np.array(h.d_res_list), rtol=htol, atol=floor, err_msg=f"{tag} dual residuals")
-    np.testing.assert_allclose(norm(L.M_XSHIFT), np.array(h.x_shift_list), rtol=htol, atol=floor, err_msg=f"{tag} x shift")
-    np.testing.assert_allclose(norm(L.M_RECOVER), np.array(h.recover_list), rtol=htol, atol=floor, err_msg=f"{tag} ||Hx-y||")
-    np.testing.assert_allclose(mean(L.M_GLR), np.array(h.GLR_list), rtol=htol, err_msg=f"{tag} GLR")
-    np.testing.assert_allclose(mean(L.M_DGTV), np.array(h.DGTV_list), rtol=htol, err_msg=f"{tag} DGTV")
-    np.testing.assert_allclose(mean(L.M_DGLR), np.array(h.DGLR_list), rtol=htol, err_msg=f"{tag} DGLR")
-    for nm in ("CG_iter_x", "CG_iter_zu", "CG_iter_zd"):
-        got = torch.stack(getattr(blk, nm)).numpy()[:, idx]
-        ref = np.array(getattr(h, nm)).reshape(n_it, -1)
-        assert (got > 0).all(), (tag, nm, "CG did not converge")
-        assert np.abs(got - ref).max() <= slack, (tag, nm, np.abs(got - ref).max())
 
 
 def _solve(blk, y, iters):
