@@ -57,6 +57,22 @@ typedef enum { MGADMM_PATH_AUTO = 0, MGADMM_PATH_STREAM = 1, MGADMM_PATH_LDS = 2
  *   BATCH_MAX   the reference's literal test sqrt(rr).max() < CG_tol (ADMM.py:360): every sample keeps iterating until the
  *               largest residual of the batch is below the tolerance; one iteration count per solve.  Streaming path only. */
 typedef enum { MGADMM_CG_PER_SAMPLE = 0, MGADMM_CG_BATCH_MAX = 1 } mgadmm_cg_convergence_t;
+/* What the stop test of the outer ADMM loop (check_stop, ADMM.py:645-646) looks at.
+ *   WHOLE_BATCH  the reference's literal test on the residual norms of the whole batch (default): one iteration count per
+ *                solve; the norms grow with sqrt(B), so the same data stops later the larger the batch is
+ *   PER_SAMPLE   sample b stops after iteration i when the largest of ITS primal and the largest of ITS dual residual norms
+ *                (square roots of the MGADMM_M_PRI_* / MGADMM_M_DUAL_* sums of metrics_per_sample the ablation has) are below
+ *                admm_tol: the reference's test on a batch of one.  n_b = i + 1 (max_admm_iter if it never passes); after
+ *                that the sample's x and state no longer change, x_out[b] / state_out[b] hold the state after iteration
+ *                n_b - 1, and n_b, x_out[b] and the state equal the B = 1 solve of that sample bit for bit.  History:
+ *                n_iters = max_b n_b; n_iters_per_sample[b] = n_b; rows i >= n_b of sample b are 0 in cg_iters and NaN in
+ *                metrics_per_sample (and stay NaN in cg_alpha / cg_beta); metrics[i] is formed from the per-sample sums as
+ *                if a stopped sample stood still (its XSHIFT / DUAL_* terms contribute 0, its PRI_*, GLR, DGTV, DGLR and
+ *                RECOVER terms their values at iteration n_b - 1); delta_x_per_step is NOT written.  With check_stop = 0
+ *                the mode is a fixed-count solve like WHOLE_BATCH.  mgadmm_two_loops has no stop test and ignores it.
+ *                LDS-resident float32 path only: together with MGADMM_PATH_STREAM, MGADMM_F64, MGADMM_CG_BATCH_MAX or a
+ *                graph the LDS path cannot hold -> MGADMM_ERR_UNSUPPORTED (solver_create / set_params). */
+typedef enum { MGADMM_ADMM_WHOLE_BATCH = 0, MGADMM_ADMM_PER_SAMPLE = 1 } mgadmm_admm_convergence_t;
 
 /* Number of per-iteration scalar diagnostics (order below) : ADMM.py:609-637 */
 #define MGADMM_NMETRIC 11
@@ -112,17 +128,20 @@ typedef struct {
     int32_t record_cg_coeffs;    /* 1: keep alpha/beta of every CG iteration (alpha_x ... beta_zd lists) */
     int32_t cg_convergence;      /* mgadmm_cg_convergence_t */
     int32_t max_inner_iter;      /* max_inner_iter = 100: inner iterations of mgadmm_two_loops (ADMM.py:77, 448) */
+    int32_t admm_convergence;    /* mgadmm_admm_convergence_t: stop test of the outer loop (default 0 = whole batch) */
 } mgadmm_params;
 
 /* Host buffers for the residual history; any pointer may be NULL.  Filled by mgadmm_solve. */
 typedef struct {
     int32_t n_iters;             /* out: ADMM iterations executed                                   */
     double* metrics;             /* [max_admm_iter][MGADMM_NMETRIC] whole-batch values (norms, not squares) */
-    double* delta_x_per_step;    /* [max_admm_iter][T]   ||mean_b(x-x_old)|| over nodes, per time step */
+    double* delta_x_per_step;    /* [max_admm_iter][T]   ||mean_b(x-x_old)|| over nodes, per time step; not written by a
+                                    solve that stops per sample (MGADMM_ADMM_PER_SAMPLE with check_stop)              */
     int32_t* cg_iters;           /* [max_admm_iter][3][B] CG iterations of x, zu, zd per sample (-1 = hit max) */
     double* metrics_per_sample;  /* [max_admm_iter][MGADMM_NMETRIC][B] per-sample sums (squares for norms) */
     double* cg_alpha;            /* [max_admm_iter][3][max_cg_iter][B] (needs record_cg_coeffs), NaN past the end */
     double* cg_beta;             /* same shape */
+    int32_t* n_iters_per_sample; /* [B] ADMM iterations of every sample (= n_iters unless MGADMM_ADMM_PER_SAMPLE) */
 } mgadmm_history;
 
 /* Device tensors of the ADMM state (API layout (B,T,N), solver dtype).  As the `state_out` of a solve: optional outputs,
@@ -136,8 +155,8 @@ typedef struct mgadmm_graph mgadmm_graph;
 typedef struct mgadmm_solver mgadmm_solver;
 
 /* "mgadmm <major>.<minor>.<patch> (gfx950)".  The minor number changes whenever a struct of this header grows (0.2:
- * mgadmm_params gained cg_convergence and max_inner_iter): a caller built against an older header must be rebuilt --
- * compare the string before passing structs. */
+ * mgadmm_params gained cg_convergence and max_inner_iter; 0.3: mgadmm_params gained admm_convergence, mgadmm_history gained
+ * n_iters_per_sample): a caller built against an older header must be rebuilt -- compare the string before passing structs. */
 const char* mgadmm_version(void);
 const char* mgadmm_last_error(void);
 

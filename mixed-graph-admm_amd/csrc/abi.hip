@@ -13,6 +13,8 @@ int mgadmm_solver_create(mgadmm_graph* g, const mgadmm_params* p, int32_t max_ba
     MG_REQUIRE(p->max_cg_iter >= 1 && p->max_admm_iter >= 1, "solver_create: iteration limits must be >= 1");
     MG_REQUIRE(p->cg_convergence == MGADMM_CG_PER_SAMPLE || p->cg_convergence == MGADMM_CG_BATCH_MAX,
                "solver_create: cg_convergence should be per_sample (0) or batch_max (1), got %d", p->cg_convergence);
+    MG_REQUIRE(p->admm_convergence == MGADMM_ADMM_WHOLE_BATCH || p->admm_convergence == MGADMM_ADMM_PER_SAMPLE,
+               "solver_create: admm_convergence should be whole_batch (0) or per_sample (1), got %d", p->admm_convergence);
     if (p->path == MGADMM_PATH_LDS && p->cg_convergence == MGADMM_CG_BATCH_MAX) {
         mg_set_error("solver_create: the LDS-resident path implements per-sample CG convergence only (batch_max: streaming path)");
         return MGADMM_ERR_UNSUPPORTED;

@@ -98,6 +98,10 @@ struct Engine : EngineBase {
     int lds_async = 1;            // MGADMM_LDS_ASYNC=0: one stream, the host tests the stop criterion after every iteration
     int* d_stop = nullptr;
     double* d_ps_ring = nullptr;  // [LDS_SETS][J][NMETRIC][Bp]: per-sample metric sums of the chunked schedule
+    // per-sample stop of the outer loop (MGADMM_ADMM_PER_SAMPLE)
+    int* d_pstop = nullptr;       // [Bp_max] stop words, [1] number of stopped samples, [Bp_max] iterations of every sample
+    double* d_ps_full = nullptr;  // [max_admm_iter][NMETRIC][Bp]: per-sample metric sums of every iteration (allocated on first use)
+    size_t ps_full_elems = 0;
     std::vector<float*> lds_ring_extra;   // iterate buffers beyond the 15 workspace vectors (chunks longer than 7 iterations)
     int64_t lds_instance = -1;       // MGADMM_Q_LDS_INSTANCE: template arguments of the k_admm_lds instance of the last launch
     int lds_chunk = LDS_MAXJ_POOL;   // MGADMM_LDS_CHUNK: ADMM iterations per k_admm_lds launch when the iteration count is fixed (1 .. LDS_MAXJ_POOL)
@@ -124,7 +128,7 @@ struct Engine : EngineBase {
         auto fr = [](void* q) { if (q) (void)hipFree(q); };
         fr(vec_pool); fr(partials); fr(d_rr); fr(d_alpha); fr(d_beta); fr(d_alpha_hist); fr(d_beta_hist);
         fr(d_active); fr(d_iters_tmp); fr(d_nact); fr(d_nonfinite); fr(d_ps); fr(d_hist); fr(d_dxps);
-        fr(d_dxpart); fr(d_hist_ps); fr(d_cg_iters); fr(d_lds_csr); fr(d_m2); fr(d_stop); fr(d_ps_ring);
+        fr(d_dxpart); fr(d_hist_ps); fr(d_cg_iters); fr(d_lds_csr); fr(d_m2); fr(d_stop); fr(d_ps_ring); fr(d_pstop); fr(d_ps_full);
         for (float* b : lds_ring_extra) if (b) (void)hipFree(b);
         if (st_side) (void)hipStreamDestroy(st_side);
         for (auto& e : ev_main) if (e) (void)hipEventDestroy(e);
@@ -468,6 +472,24 @@ struct Engine : EngineBase {
         for (auto& e : ev_ring) MG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         MG_TRY(alloc_iter_dependent());
         MG_TRY(plan_lds());
+        return check_admm_convergence(p, "solver_create");
+    }
+
+    // The per-sample stop test of the outer loop lives in the LDS-resident kernel (one workgroup owns a sample); the streaming
+    // kernels are batch-innermost and would need per-sample masks throughout (like MGADMM_CG_BATCH_MAX is streaming-only).
+    int check_admm_convergence(const mgadmm_params& np, const char* who) const {
+        MG_REQUIRE(np.admm_convergence == MGADMM_ADMM_WHOLE_BATCH || np.admm_convergence == MGADMM_ADMM_PER_SAMPLE,
+                   "%s: admm_convergence should be whole_batch (0) or per_sample (1), got %d", who, np.admm_convergence);
+        if (np.admm_convergence != MGADMM_ADMM_PER_SAMPLE) return MGADMM_OK;
+        const char* why = nullptr;
+        if (!std::is_same<S, float>::value) why = "float64 arithmetic runs on the streaming path";
+        else if (np.path == MGADMM_PATH_STREAM) why = "path is MGADMM_PATH_STREAM";
+        else if (np.cg_convergence == MGADMM_CG_BATCH_MAX) why = "cg_convergence batch_max runs on the streaming path";
+        else if (!lds.ok) why = "the LDS-resident path cannot hold this graph (it needs T*N*8 B + tables <= 160 KiB and N*G <= 1024)";
+        if (why) {
+            mg_set_error("%s: admm_convergence per_sample is implemented by the LDS-resident float32 path only: %s", who, why);
+            return MGADMM_ERR_UNSUPPORTED;
+        }
         return MGADMM_OK;
     }
 
@@ -507,6 +529,7 @@ struct Engine : EngineBase {
             mg_set_error("set_params: the LDS-resident path implements per-sample CG convergence only (batch_max: streaming path)");
             return MGADMM_ERR_UNSUPPORTED;
         }
+        MG_TRY(check_admm_convergence(np, "set_params"));
         p = np;
         sv->p = np;
         MG_HIP(hipSetDevice(g->device));
@@ -1094,6 +1117,7 @@ struct Engine : EngineBase {
             return MGADMM_ERR_UNSUPPORTED;
         }
         if (use_lds()) return solve_lds(y, mask, B, x0, state_in, x_out, state_out, hist);
+        MG_TRY(check_admm_convergence(p, "solve"));       // (refused at solver_create / set_params already)
         const Geom q = make_geom(B);
         MG_TRY(ensure_partials(q));
         const size_t ne = velems(q);
@@ -1570,6 +1594,7 @@ struct Engine : EngineBase {
         MG_HIP(hipMalloc(&d_stop, sizeof(int)));
         MG_HIP(hipMemset(d_stop, 0, sizeof(int)));
         MG_HIP(hipMalloc(&d_ps_ring, sizeof(double) * LDS_SETS * LDS_MAXJ_POOL * MGADMM_NMETRIC * Bp_max));
+        MG_HIP(hipMalloc(&d_pstop, sizeof(int) * (2 * (size_t)Bp_max + 1)));
         {
             // helper stream of the overlapped outer loop: non-blocking (the caller's stream may be the legacy default stream,
             // which would serialise a blocking stream with itself), lowest priority (the k_admm_lds workgroups of the next
@@ -1631,7 +1656,26 @@ struct Engine : EngineBase {
             //            sums through two sets: launch c+2 overwrites what the metric kernels of chunk c read and waits for them.
             //            J = 1 is the overlapped one-iteration-per-launch schedule of round 2.
             enum { SYNC, DEVSTOP, CHUNKS };
-            const int sched = (!lds_async || record) ? SYNC : (p.check_stop ? DEVSTOP : CHUNKS);
+            // Per-sample stop (MGADMM_ADMM_PER_SAMPLE with check_stop): the test runs INSIDE k_admm_lds, after every iteration of a
+            // launch, on the sample the workgroup owns -- it needs nothing from outside the workgroup.  So the solve takes the
+            // CHUNKS schedule (SYNC when the CG coefficients are recorded): a sample that stops writes x_out[b] itself and sets
+            // its stop word, its workgroup returns at the guard of every later launch; the host reads the number of stopped
+            // samples LAG launches late and ends when it equals B.  The per-sample sums of every iteration go to a buffer of their
+            // own (no ring, no helper stream); delta_x_per_step is not formed; the whole-batch history is made at the end from the
+            // sums and the stop words (k_lds_ps_history).
+            const bool ps_mode = p.admm_convergence == MGADMM_ADMM_PER_SAMPLE && p.check_stop;
+            const int sched = (!lds_async || record) ? SYNC : ((p.check_stop && !ps_mode) ? DEVSTOP : CHUNKS);
+            if (ps_mode) {
+                const size_t need = (size_t)max_it * MGADMM_NMETRIC * Bp;
+                if (need > ps_full_elems) {
+                    if (d_ps_full) MG_HIP(hipFree(d_ps_full));
+                    d_ps_full = nullptr;
+                    ps_full_elems = 0;
+                    MG_HIP(hipMalloc(&d_ps_full, need * sizeof(double)));
+                    ps_full_elems = need;
+                }
+                MG_HIP(hipMemsetAsync(d_pstop, 0, sizeof(int) * ((size_t)Bp_max + 1), st));
+            }
             // The caller's output buffers ARE the working state of this path (same (B, T*N) layout): no copy-out at the end
             // (round 2 until here: seven 120 MB device copies per solve at cfg2 = 0.7 ms of a 59 ms solve).  The iterates are
             // assigned to buffers so that the one of the LAST iteration lands in x_out (an early stop on another buffer
@@ -1713,7 +1757,22 @@ struct Engine : EngineBase {
             a.nonfinite = d_nonfinite;
             a.stop = sched == DEVSTOP ? d_stop : nullptr;
             if (sched == DEVSTOP) MG_HIP(hipMemsetAsync(d_stop, 0, sizeof(int), st));
-            if (sched == CHUNKS) MG_HIP(hipMemsetAsync(d_ps_ring, 0, sizeof(double) * LDS_SETS * J * MGADMM_NMETRIC * Bp, st));
+            if (sched == CHUNKS && !ps_mode) MG_HIP(hipMemsetAsync(d_ps_ring, 0, sizeof(double) * LDS_SETS * J * MGADMM_NMETRIC * Bp, st));
+            int* const d_pcount = d_pstop + Bp_max;
+            if (ps_mode) {
+                a.pstop = d_pstop; a.pstop_count = d_pcount; a.x_final = xo_; a.admm_tol = p.admm_tol;
+            }
+            // number of stopped samples after launch `c`, read LAG launches late: true when every sample has stopped
+            auto all_stopped = [&](int c, bool* done) -> int {
+                MG_HIP(hipMemcpyAsync(h_flag + 1 + c % (LAG + 1), d_pcount, sizeof(int), hipMemcpyDeviceToHost, st));
+                MG_HIP(hipEventRecord(ev_ring[c % (LAG + 1)], st));
+                *done = false;
+                if (c >= LAG) {
+                    MG_HIP(hipEventSynchronize(ev_ring[(c - LAG) % (LAG + 1)]));
+                    *done = h_flag[1 + (c - LAG) % (LAG + 1)] == B;
+                }
+                return MGADMM_OK;
+            };
             const size_t K = p.max_cg_iter;
             int n_done = 0, rc_final = MGADMM_OK;
             // the whole-batch metrics of iteration `it` (delta_x_per_step, norms / means over the samples) on stream `s`
@@ -1734,6 +1793,16 @@ struct Engine : EngineBase {
                     for (int k = 0; k <= Jc; ++k) a.xs[k] = xbuf(it0 + k);
                     a.cg_iters = d_cg_iters + (size_t)it0 * 3 * Bp;
                     a.ps = d_ps_ring + (size_t)(c % LDS_SETS) * J * MGADMM_NMETRIC * Bp;
+                    if (ps_mode) {
+                        a.ps = d_ps_full + (size_t)it0 * MGADMM_NMETRIC * Bp;
+                        a.it0 = it0;
+                        MG_TRY(launch_lds(a, B));
+                        n_done = it0 + Jc;
+                        bool done = false;
+                        MG_TRY(all_stopped(c, &done));
+                        if (done) break;          // the launches enqueued since returned at their guards
+                        continue;
+                    }
                     // launch c overwrites the iterate buffers and the metric sums that the metric kernels of chunk c-3 read (interior
                     // set and metric set c % 3; boundary buffer (c + 1) % 4 = the start of chunk c-3).  Two sets / three boundary
                     // buffers (until the end of round 3) made launch c wait for the metrics of chunk c-2, which run BESIDE launch c-1
@@ -1746,7 +1815,7 @@ struct Engine : EngineBase {
                     MG_HIP(hipEventRecord(ev_side[c % LDS_NBOUND], st_side));
                     n_done = it0 + Jc;
                 }
-                if (c > 0)            // join the helper stream (its kernels run in order: the last event covers all)
+                if (c > 0 && !ps_mode)            // join the helper stream (its kernels run in order: the last event covers all)
                     MG_HIP(hipStreamWaitEvent(st, ev_side[(c - 1) % LDS_NBOUND], 0));
             }
             for (int it = 0; sched != CHUNKS && it < max_it; ++it) {
@@ -1755,12 +1824,13 @@ struct Engine : EngineBase {
                 a.xs[0] = xbuf(it); a.xs[1] = xbuf(it + 1);
                 a.cg_iters = d_cg_iters + (size_t)it * 3 * Bp;
                 a.ps = d_ps;
+                if (ps_mode) { a.ps = d_ps_full + (size_t)it * MGADMM_NMETRIC * Bp; a.it0 = it; }
                 if (record) {
                     MG_TRY(fill((S*)d_alpha_hist, 3 * K * Bp, (S)NAN));
                     MG_TRY(fill((S*)d_beta_hist, 3 * K * Bp, (S)NAN));
                 }
                 MG_TRY(launch_lds(a, B));
-                MG_TRY(batch_metrics(it, a.ps, st));
+                if (!ps_mode) MG_TRY(batch_metrics(it, a.ps, st));
                 if (record) {
                     for (int w = 0; w < 3; ++w) {
                         if (w == 2 && !has_zd) continue;
@@ -1771,7 +1841,11 @@ struct Engine : EngineBase {
                     }
                 }
                 n_done = it + 1;
-                if (sched == DEVSTOP) {
+                if (ps_mode) {            // (the host is in step with the device here: the count of this very launch)
+                    MG_HIP(hipMemcpyAsync(h_flag + 1, d_pcount, sizeof(int), hipMemcpyDeviceToHost, st));
+                    MG_HIP(hipStreamSynchronize(st));
+                    if (h_flag[1] == B) break;
+                } else if (sched == DEVSTOP) {
                     MG_TRY(mg_lds_stop_test(d_hist + (size_t)it * MGADMM_NMETRIC, d_nonfinite, has_phi, has_zd, p.admm_tol, it, d_stop, st));
                     MG_HIP(hipMemcpyAsync(h_flag + 1 + it % (LAG + 1), d_stop, sizeof(int), hipMemcpyDeviceToHost, st));
                     MG_HIP(hipEventRecord(ev_ring[it % (LAG + 1)], st));
@@ -1802,7 +1876,19 @@ struct Engine : EngineBase {
                 if (sw > 0) n_done = sw;
                 else if (sw < 0) { n_done = -sw; rc_final = MGADMM_ERR_NONFINITE; }
             }
-            float* const xc = xbuf(n_done);
+            std::vector<int> nps;         // per-sample stop: iterations of every sample
+            if (ps_mode) {
+                // n_done iterations were enqueued; the history from the stop words and the per-sample sums
+                int* const d_nps = d_pstop + Bp_max + 1;
+                MG_TRY(mg_lds_ps_history(d_ps_full, d_pstop, n_done, max_it, B, Bp, d_nps, d_hist,
+                                         (hist && hist->metrics_per_sample) ? d_hist_ps : nullptr, st));
+                nps.resize(B);
+                MG_HIP(hipMemcpyAsync(nps.data(), d_nps, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+                MG_HIP(hipStreamSynchronize(st));
+                n_done = *std::max_element(nps.begin(), nps.end());
+            }
+            // (per-sample stop: a stopped sample stored x_out[b] itself, the others ran max_it iterations and xbuf(max_it) = x_out)
+            float* const xc = ps_mode ? xo_ : xbuf(n_done);
             if (xc != xo_)        // early stop on the other parity
                 MG_HIP(hipMemcpyAsync(x_out, xc, (size_t)B * TN * sizeof(float), hipMemcpyDeviceToDevice, st));
             if (state_out) {      // the state the caller asked for, in the reference's layout
@@ -1818,17 +1904,20 @@ struct Engine : EngineBase {
                 MG_TRY(out(state_out->gamma_u, gu));
                 MG_TRY(out(state_out->gamma_d, gd));
             }
-            return finish_history(hist, n_done, B, Bp, rc_final);
+            return finish_history(hist, n_done, B, Bp, rc_final, ps_mode ? nps.data() : nullptr);
         }
     }
 
     // copies the device-side history of a finished solve into the caller's host buffers
-    int finish_history(mgadmm_history* hist, int n_done, int B, int Bp, int rc_final) {
+    // nps: iterations of every sample of a solve that stopped per sample (its delta_x_per_step is not formed), else nullptr
+    int finish_history(mgadmm_history* hist, int n_done, int B, int Bp, int rc_final, const int* nps = nullptr) {
         if (hist) {
             hist->n_iters = n_done;
+            if (hist->n_iters_per_sample)
+                for (int b = 0; b < B; ++b) hist->n_iters_per_sample[b] = nps ? nps[b] : n_done;
             if (hist->metrics)
                 MG_HIP(hipMemcpyAsync(hist->metrics, d_hist, sizeof(double) * (size_t)n_done * MGADMM_NMETRIC, hipMemcpyDeviceToHost, st));
-            if (hist->delta_x_per_step)
+            if (hist->delta_x_per_step && !nps)
                 MG_HIP(hipMemcpyAsync(hist->delta_x_per_step, d_dxps, sizeof(double) * (size_t)n_done * T, hipMemcpyDeviceToHost, st));
             if (hist->metrics_per_sample)
                 MG_HIP(hipMemcpyAsync(hist->metrics_per_sample, d_hist_ps, sizeof(double) * (size_t)n_done * MGADMM_NMETRIC * B,

@@ -49,6 +49,14 @@ struct LdsArgsCore {
 struct LdsArgs : LdsArgsCore {
     float* xs[LDS_MAXJ + 1];   // trip k reads the iterate xs[k] and writes xs[k + 1] (every iterate is kept: delta_x_per_step);
                                // indexed by the trip number straight from the kernarg segment
+    // Per-sample stop of the outer loop (MGADMM_ADMM_PER_SAMPLE with check_stop; read by the kernels k_admm_lds_ps only, which a
+    // launch takes when pstop != nullptr; behind xs: the offsets of everything k_admm_lds reads stay what they were): the workgroup tests its own sample after every trip
+    int* pstop;            // [Bp] stop word of every sample: 0 = running, n_b = iterations it ran once it has stopped; a workgroup
+                           // whose word is set returns at its first instruction
+    int* pstop_count;      // number of samples that have stopped (the host ends the solve when it reads B)
+    float* x_final;        // (B, TN): a sample that stops stores its iterate here itself (the iterate buffers of a chunk rotate)
+    double admm_tol;       // ADMM_tol
+    int it0;               // number of the launch's first iteration in this solve (n_b = it0 + trip + 1)
 };
 
 // Execution plan of k_admm_lds chosen by Engine::plan_lds
@@ -66,6 +74,8 @@ struct LdsLaunch {
 
 // J ADMM iterations for B samples (one workgroup per sample); returns a mgadmm_status
 int mg_lds_iteration(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t st);
+// the same with the per-sample stop test (a.pstop != nullptr; mg_lds_iteration forwards to it)
+int mg_lds_iteration_ps(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t st);
 // initial state (ADMM.py:528-544): x in the reference's sample-major layout, zu / zd / gamma* thread-major for time groups of TPG steps
 int mg_lds_init(bool masked, int T, int t_in, int N, int TPG, int B, float tm, float den, const float* y, const float* mask, float* x,
                 float* zu, float* zd, float* gam, float* gu, float* gd, int* nonfinite, hipStream_t st);
@@ -74,6 +84,12 @@ int mg_lds_state_layout(bool to_thread_major, int T, int N, int TPG, int B, cons
 // delta_x_per_step on the sample-major layout (ADMM.py:614): scratch = double[TN * (1 + ceil(B/64))], out = double[T];
 // stop: device stop word (the kernels return at once when it is set) or nullptr
 int mg_lds_dxps(int T, int N, int B, const float* x, const float* xo, double* scratch, double* out, const int* stop, hipStream_t st);
+// History of a solve that stopped per sample, from the stop words and the per-sample metric sums ps = [n_it][NMETRIC][Bp] of
+// all n_it iterations enqueued: n_per_sample[b] = n_b (max_it for a sample that never stopped); metrics[n_it][NMETRIC] = the
+// whole-batch values as if a stopped sample stood still (difference terms 0, the others as at its last iteration);
+// out_ps (or nullptr) = [n_it][NMETRIC][B] the sums, NaN for the rows past n_b
+int mg_lds_ps_history(const double* ps, const int* pstop, int n_it, int max_it, int B, int Bp, int* n_per_sample, double* metrics,
+                      double* out_ps, hipStream_t st);
 // stop test of one ADMM iteration on the device (ADMM.py:645-646 + the NaN asserts): *stop = it + 1 when both residual maxima
 // are below tol, -(it + 1) when a metric or the iterate is not finite; leaves a stop word that is already set alone
 int mg_lds_stop_test(const double* metrics_row, const int* nonfinite, int has_phi, int has_zd, double tol, int it, int* stop, hipStream_t st);

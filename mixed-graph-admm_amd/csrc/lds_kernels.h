@@ -773,8 +773,22 @@ __device__ __forceinline__ int lds_cg(LdsCtx<TPG, BAND, NU, ND, TP>& c, BlockRed
 // NU / ND > 0: every row of W_u / W_d holds exactly that many entries (a kNN table without pads): unrolled gathers, the
 // rows are read from the global image (L2) into registers once per solve and only the W_d^T tail table lives in LDS.
 // SLOTS: two more LDS vectors park per-thread operands across the solves (see the trip body).
+// PS (MGADMM_LDS_PER_SAMPLE_STOP, defined by lds_launch_ps.hip): per-sample stop of the outer loop (MGADMM_ADMM_PER_SAMPLE) --
+// after every trip the workgroup tests the residuals of its own sample against ADMM_tol (LdsArgs::pstop ...).  A compile-time
+// flag of the translation unit, not a launch argument and not a template parameter: the instances of the default mode
+// (lds_launch.hip) are compiled from the very code they had before the mode existed and keep their names -- their register
+// allocation is fragile (profiles/r04/kernel_registers.txt: moving the body into a function shared by two kernels already
+// changed the spill counts of 30 of them); the instances with the test are the kernels k_admm_lds_ps of lds_launch_ps.hip.
+#ifdef MGADMM_LDS_PER_SAMPLE_STOP
+#define MG_LDS_KERNEL k_admm_lds_ps
+#define MG_LDS_PS true
+#else
+#define MG_LDS_KERNEL k_admm_lds
+#define MG_LDS_PS false
+#endif
 template <int TPG, bool BAND, int MAXT, bool SB, int NU = 0, int ND = 0, bool SLOTS = false, int TP = -1>
-__global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void k_admm_lds(LdsArgs a_in) {
+__global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERNEL(LdsArgs a_in) {
+    constexpr bool PS = MG_LDS_PS;
     constexpr bool ENTG = NU > 0 && ND > 0;       // table rows from the global image
     constexpr int NMRED = 12;                     // metric slots per wave (MGADMM_NMETRIC = 11)
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -792,6 +806,9 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void k_admm_lds(
     // ADMM outer loop without host round trips: iterations are enqueued ahead of the host's look at the stop test, a launch
     // that follows the stopping iteration must leave the state alone (workgroup-uniform scalar load)
     if (a_in.stop != nullptr && *a_in.stop != 0) return;
+    if constexpr (PS) {       // this sample stopped in an earlier launch: its state and x_out[b] are final (workgroup-uniform scalar load)
+        if (a_in.pstop[b] != 0) return;
+    }
     // STAGGERED START.  Samples of one batch need (nearly) the same CG iteration counts, so the workgroups of a launch
     // run in lock step: all CUs store their results and request the next sample's operands at the same moment, while HBM
     // idles during the CG solves.  The workgroups of the first round (one per CU) start spread over `stagger_ticks`,
@@ -1345,6 +1362,34 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void k_admm_lds(
         cgi[a.Bp + b] = itzu;
         cgi[2 * a.Bp + b] = itzd;
     }
+    if constexpr (PS) {
+        // PER-SAMPLE STOP TEST (ADMM.py:645-646 on a batch of one).  Every thread forms the residual sums of the sample from the
+        // wave totals in LDS (broadcast reads; the association of the sums stored to `ps` above: the same doubles) and takes the
+        // square roots and comparisons of k_batch_metrics + k_lds_stop_test at B = 1 -- the decision is workgroup-uniform
+        // without another barrier, and equal to the one the B = 1 solve of this sample takes.  (mred is written next by the
+        // metrics of the following trip, behind the barriers of its x solve.)
+        auto rnorm = [&](int m) {
+            float sj[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                sj[j] = (mred[j * NMRED + m] + mred[(j + 4) * NMRED + m]) + (mred[(j + 8) * NMRED + m] + mred[(j + 12) * NMRED + m]);
+            return sqrt((double)((sj[0] + sj[1]) + (sj[2] + sj[3])));
+        };
+        double pri = rnorm(MGADMM_M_PRI_ZU), dual = rnorm(MGADMM_M_DUAL_ZU);
+        if (has_phi) { pri = fmax(pri, rnorm(MGADMM_M_PRI_PHI)); dual = fmax(dual, rnorm(MGADMM_M_DUAL_PHI)); }
+        if (has_zd) { pri = fmax(pri, rnorm(MGADMM_M_PRI_ZD)); dual = fmax(dual, rnorm(MGADMM_M_DUAL_ZD)); }
+        const double atol = a.admm_tol;
+        if (pri < atol && dual < atol) {
+            // the sample ends here: its iterate goes to x_out[b] (nobody can fetch it from the rotating buffers of the chunk
+            // later), the state vectors hold what this trip stored, and no later trip or launch touches either
+            c.putg(a.x_final + sb, xc);
+            if (tid == 0) {
+                a.pstop[b] = a.it0 + trip + 1;
+                atomicAdd(a.pstop_count, 1);
+            }
+            break;
+        }
+    }
     }       // trips
 }
 
@@ -1440,7 +1485,7 @@ __global__ __launch_bounds__(256) void k_state_layout(int T, int N, int TPG, con
 
 // delta_x_per_step on the sample-major layout.  Pass 1: workgroup (e-block, b-slice) sums x - x_old over
 // its 64 samples -> part[slice][e].  Pass 2: fixed-order sum over the slices, mean, square -> m2[e].
-__global__ __launch_bounds__(256) void k_dxps_sm(int TN, int B, const float* __restrict__ x, const float* __restrict__ xo,
+static __global__ __launch_bounds__(256) void k_dxps_sm(int TN, int B, const float* __restrict__ x, const float* __restrict__ xo,
                                                  double* __restrict__ part, const int* __restrict__ stop) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= TN || (stop != nullptr && *stop != 0)) return;
@@ -1455,7 +1500,7 @@ __global__ __launch_bounds__(256) void k_dxps_sm(int TN, int B, const float* __r
 // One-wave workgroups: in the overlapped schedule of the outer loop (Engine::solve_lds) this kernel runs beside the k_admm_lds
 // launch of the next iteration, whose workgroup leaves room for single waves only (its 15 waves fill three of the four SIMDs
 // of a CU; the fourth has 128 free VGPRs)
-__global__ __launch_bounds__(64) void k_dxps_sm4(int TN, int B, const float* __restrict__ x, const float* __restrict__ xo,
+static __global__ __launch_bounds__(64) void k_dxps_sm4(int TN, int B, const float* __restrict__ x, const float* __restrict__ xo,
                                                  double* __restrict__ part, const int* __restrict__ stop) {
     const int e = (blockIdx.x * 64 + threadIdx.x) * 4;
     if (e >= TN || (stop != nullptr && *stop != 0)) return;
@@ -1489,7 +1534,7 @@ __global__ __launch_bounds__(64) void k_dxps_sm4(int TN, int B, const float* __r
     dst[0] = s0; dst[1] = s1; dst[2] = s2; dst[3] = s3;
 }
 
-__global__ __launch_bounds__(256) void k_dxps_sm_mean(int TN, int B, int nslices, const double* __restrict__ part,
+static __global__ __launch_bounds__(256) void k_dxps_sm_mean(int TN, int B, int nslices, const double* __restrict__ part,
                                                       double* __restrict__ m2, const int* __restrict__ stop) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= TN || (stop != nullptr && *stop != 0)) return;
@@ -1507,7 +1552,7 @@ __global__ __launch_bounds__(256) void k_dxps_sm_mean(int TN, int B, int nslices
     m2[e] = s * s;
 }
 
-__global__ void k_dxps_sm_final(int T, int N, const double* __restrict__ m2, double* __restrict__ out, const int* __restrict__ stop) {
+static __global__ void k_dxps_sm_final(int T, int N, const double* __restrict__ m2, double* __restrict__ out, const int* __restrict__ stop) {
     const int t = blockIdx.x;
     if (stop != nullptr && *stop != 0) return;          // uniform
     __shared__ double sm[256];
@@ -1524,7 +1569,7 @@ __global__ void k_dxps_sm_final(int T, int N, const double* __restrict__ m2, dou
 
 // Stop test of one ADMM iteration, on the device (the host's test of the synchronous loop, Engine::solve_lds): row = the
 // whole-batch metrics of iteration `it` (k_batch_metrics).  One lane.
-__global__ void k_lds_stop_test(const double* __restrict__ row, const int* __restrict__ nonfinite, int has_phi, int has_zd, double tol,
+static __global__ void k_lds_stop_test(const double* __restrict__ row, const int* __restrict__ nonfinite, int has_phi, int has_zd, double tol,
                                 int it, int* __restrict__ stop) {
     if (threadIdx.x != 0 || *stop != 0) return;
     bool finite = *nonfinite == 0;
@@ -1534,4 +1579,41 @@ __global__ void k_lds_stop_test(const double* __restrict__ row, const int* __res
     if (has_phi) { pri = fmax(pri, row[MGADMM_M_PRI_PHI]); dual = fmax(dual, row[MGADMM_M_DUAL_PHI]); }
     if (has_zd) { pri = fmax(pri, row[MGADMM_M_PRI_ZD]); dual = fmax(dual, row[MGADMM_M_DUAL_ZD]); }
     if (pri < tol && dual < tol) *stop = it + 1;
+}
+
+// History of a solve that stopped per sample (MGADMM_ADMM_PER_SAMPLE).  ps = [n_it][NMETRIC][Bp]: the per-sample sums of every
+// iteration enqueued (a sample's rows past its stop were never written); pstop = the stop words.  Workgroup (i, m):
+// metrics[i][m] = the whole-batch value of iteration i as if a stopped sample stood still -- its difference terms (x shift,
+// dual residuals) contribute 0, its other terms their values at its last iteration n_b - 1 -- summed over the samples in the
+// fixed order of k_batch_metrics (B = 1: the same value); out_ps[i][m][b] = the sum, NaN for i >= n_b.
+// Workgroup (0, 0) also writes n_b (max_it for a sample that never stopped).  (Other workgroups read rows < n_b only: no
+// row is read that another one fills.)
+static __global__ __launch_bounds__(256) void k_lds_ps_history(const double* __restrict__ ps, const int* __restrict__ pstop, int max_it,
+                                                               int B, int Bp, int* __restrict__ n_per_sample,
+                                                               double* __restrict__ metrics, double* __restrict__ out_ps) {
+    const int i = blockIdx.x, m = blockIdx.y;
+    const bool is_diff = (m == MGADMM_M_XSHIFT || m == MGADMM_M_DUAL_ZU || m == MGADMM_M_DUAL_PHI || m == MGADMM_M_DUAL_ZD);
+    __shared__ double sm[256];
+    double s = 0.0;
+    for (int c = threadIdx.x; c < B; c += 256) {
+        const int w = pstop[c];
+        const int nb = w > 0 ? w : max_it;
+        if (i == 0 && m == 0) n_per_sample[c] = nb;
+        const bool runs = i < nb;
+        const double v = runs ? ps[((size_t)i * MGADMM_NMETRIC + m) * Bp + c]
+                              : (is_diff ? 0.0 : ps[((size_t)(nb - 1) * MGADMM_NMETRIC + m) * Bp + c]);
+        s += v;
+        if (out_ps) out_ps[((size_t)i * MGADMM_NMETRIC + m) * B + c] = runs ? v : __longlong_as_double(0x7ff8000000000000LL);
+    }
+    sm[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) sm[threadIdx.x] += sm[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double tot = sm[0];
+        const bool is_mean = (m == MGADMM_M_GLR || m == MGADMM_M_DGTV || m == MGADMM_M_DGLR);
+        metrics[(size_t)i * MGADMM_NMETRIC + m] = is_mean ? tot / (double)B : sqrt(tot);
+    }
 }

@@ -64,15 +64,23 @@ class ADMM_algorithm():
                       are B independent reference runs; 'batch_max': the reference's literal test
                       ``sqrt(rr).max() < CG_tol`` (ADMM.py:360) -- all samples iterate until the largest residual of
                       the batch is below the tolerance (streaming kernels only; one count per solve)
+      admm_convergence  'whole_batch' (default): the reference's stop test of the outer loop (ADMM.py:645-646) on the
+                      residual norms of the whole batch; 'per_sample': every sample stops on its own residuals, as if it
+                      were solved alone (B samples = B independent B=1 runs, bit for bit).  ``solve`` then leaves the
+                      iteration count of every sample in ``n_iters_per_sample``; the residual lists count a stopped
+                      sample as standing still, ``delta_x_per_step`` stays empty.  LDS-resident float32 path only.
     """
 
     def __init__(self, graph_info, ADMM_info, use_kNN=False, k=4, u_sigma=None, d_sigma=None, expand_time_dim=True,
                  ablation='None', t_in=12, T=24, use_line_graph=False, skip_connection=1, *, device=None,
                  compute_dtype=torch.float32, bug_compat=True, tables=None, reorder='auto', record_cg_coeffs='auto',
-                 path='auto', graph_backend='auto', cg_convergence='per_sample'):
+                 path='auto', graph_backend='auto', cg_convergence='per_sample', admm_convergence='whole_batch'):
         if cg_convergence not in ('per_sample', 'batch_max'):
             raise ValueError(f"cg_convergence must be 'per_sample' or 'batch_max', got {cg_convergence!r}")
         self.cg_convergence = cg_convergence
+        if admm_convergence not in ('whole_batch', 'per_sample'):
+            raise ValueError(f"admm_convergence must be 'whole_batch' or 'per_sample', got {admm_convergence!r}")
+        self.admm_convergence = admm_convergence
         if graph_backend not in ('auto', 'host', 'gpu'):
             raise ValueError(f"graph_backend must be 'auto', 'host' or 'gpu', got {graph_backend!r}")
         if graph_backend == 'auto':
@@ -145,6 +153,7 @@ class ADMM_algorithm():
         self.CG_iter_x, self.CG_iter_zu, self.CG_iter_zd = [], [], []
         self.p_res_list, self.d_res_list, self.x_shift_list, self.delta_x_per_step = [], [], [], []
         self.DGTV_list, self.DGLR_list, self.GLR_list, self.recover_list = [], [], [], []
+        self.n_iters_per_sample = None      # numpy int32[B] after a solve: ADMM iterations of every sample
 
     def init_iterations(self, ablation, use_line_graph=False):
         """Reset the history and switch ablation / temporal graph (ADMM.py:100-133).  Like the reference: the history
@@ -251,6 +260,9 @@ class ADMM_algorithm():
         p.record_cg_coeffs = int(bool(rec))
         p.cg_convergence = _lib.CG_BATCH_MAX if self.cg_convergence == 'batch_max' else _lib.CG_PER_SAMPLE
         p.max_inner_iter = int(self.max_inner_iter)
+        if self.admm_convergence not in ('whole_batch', 'per_sample'):
+            raise ValueError(f"admm_convergence must be 'whole_batch' or 'per_sample', got {self.admm_convergence!r}")
+        p.admm_convergence = _lib.ADMM_PER_SAMPLE if self.admm_convergence == 'per_sample' else _lib.ADMM_WHOLE_BATCH
         return p
 
     def _solver(self, Cn, dtype, B):
@@ -466,6 +478,11 @@ class ADMM_algorithm():
         hs.metrics = metrics.ctypes.data_as(C.POINTER(C.c_double))
         hs.delta_x_per_step = dxps.ctypes.data_as(C.POINTER(C.c_double))
         hs.cg_iters = cg_it.ctypes.data_as(C.POINTER(C.c_int32))
+        nps = np.zeros(B, dtype=np.int32)
+        hs.n_iters_per_sample = nps.ctypes.data_as(C.POINTER(C.c_int32))
+        if p.admm_convergence == _lib.ADMM_PER_SAMPLE:
+            dxps = None               # not formed when samples stop on their own (include/mgadmm.h)
+            hs.delta_x_per_step = None
         mps = None
         if per_sample_history:
             mps = np.zeros((I, _lib.NMETRIC, B), dtype=np.float64)
@@ -493,9 +510,12 @@ class ADMM_algorithm():
             rc = _lib.lib.mgadmm_solve_from(h, _ptr(yd), _ptr(md), mask_f32, B, _ptr(win["x"]), C.byref(sin), _ptr(x),
                                             C.byref(st), C.byref(hs), _stream_ptr(dev))
         n = hs.n_iters
+        self.n_iters_per_sample = nps
+        if dxps is not None:
+            dxps = dxps[:n]
         if rc == _lib.ERR_NONFINITE:
             # like the reference at its asserts (ADMM.py:534-606), the history of the iterations that ran is available
-            self._fill_history(metrics[:n], dxps[:n], cg_it[:n], al, be, B, has_phi, has_zd, False)
+            self._fill_history(metrics[:n], dxps, cg_it[:n], al, be, B, has_phi, has_zd, False)
             bad = ""
             if mps is not None:
                 self.metrics_per_sample = mps[:n]
@@ -505,7 +525,7 @@ class ADMM_algorithm():
             raise AssertionError("NaN/Inf value in the ADMM iterates (reference asserts, ADMM.py:534-606): "
                                  + _lib.lib.mgadmm_last_error().decode() + bad)
         _lib.check(rc)
-        self._fill_history(metrics[:n], dxps[:n], cg_it[:n], al, be, B, has_phi, has_zd, print_info)
+        self._fill_history(metrics[:n], dxps, cg_it[:n], al, be, B, has_phi, has_zd, print_info)
         if mps is not None:
             self.metrics_per_sample = mps[:n]
         back = lambda t: t.to(device=y.device, dtype=y.dtype)
@@ -525,7 +545,7 @@ class ADMM_algorithm():
     def history(self):
         keys = ("p_res_list", "d_res_list", "x_shift_list", "delta_x_per_step", "GLR_list", "DGTV_list", "DGLR_list",
                 "recover_list", "CG_iter_x", "CG_iter_zu", "CG_iter_zd", "alpha_x", "beta_x", "alpha_zu", "beta_zu",
-                "alpha_zd", "beta_zd", "res_name")
+                "alpha_zd", "beta_zd", "res_name", "n_iters_per_sample")
         return {k2: getattr(self, k2) for k2 in keys}
 
     def _fill_history(self, metrics, dxps, cg_it, al, be, B, has_phi, has_zd, print_info):
@@ -534,7 +554,8 @@ class ADMM_algorithm():
             m = metrics[i]
             pri, dual = [float(m[L.M_PRI_ZU])], [float(m[L.M_DUAL_ZU])]
             self.x_shift_list.append(float(m[L.M_XSHIFT]))
-            self.delta_x_per_step.append(torch.tensor(dxps[i]))
+            if dxps is not None:
+                self.delta_x_per_step.append(torch.tensor(dxps[i]))
             self.GLR_list.append(torch.tensor(m[L.M_GLR]))
             self.recover_list.append(float(m[L.M_RECOVER]))
             if has_phi:

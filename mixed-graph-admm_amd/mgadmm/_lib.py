@@ -20,6 +20,7 @@ F32, F64 = 0, 1
 TEMPORAL_SPATIAL, TEMPORAL_BAND = 0, 1
 OP_LU, OP_LDR, OP_LDRT, OP_CLDR, OP_LN = 0, 1, 2, 3, 4
 CG_PER_SAMPLE, CG_BATCH_MAX = 0, 1
+ADMM_WHOLE_BATCH, ADMM_PER_SAMPLE = 0, 1
 LHS_X, LHS_ZU, LHS_ZD = 0, 1, 2
 ABLATIONS = {"None": 0, "DGTV": 1, "DGLR": 2, "UT": 3}
 PATH_AUTO, PATH_STREAM, PATH_LDS = 0, 1, 2
@@ -55,6 +56,7 @@ class Params(C.Structure):
         ("admm_tol", C.c_double), ("max_admm_iter", C.c_int32),
         ("dtype", C.c_int32), ("check_stop", C.c_int32), ("path", C.c_int32),
         ("record_cg_coeffs", C.c_int32), ("cg_convergence", C.c_int32), ("max_inner_iter", C.c_int32),
+        ("admm_convergence", C.c_int32),
     ]
 
 
@@ -63,6 +65,7 @@ class History(C.Structure):
         ("n_iters", C.c_int32),
         ("metrics", _f64p), ("delta_x_per_step", _f64p), ("cg_iters", _i32p),
         ("metrics_per_sample", _f64p), ("cg_alpha", _f64p), ("cg_beta", _f64p),
+        ("n_iters_per_sample", _i32p),
     ]
 
 
