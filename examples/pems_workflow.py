@@ -3,6 +3,7 @@
 
     files -> TrafficDataset (series resident on the GPU) -> kNN graph -> ADMM_algorithm
           -> prediction of the next 12 steps for a whole batch of sliding windows
+          -> grid search over two ADMM weights on the first 16 windows, all cells in one batch
           -> interpolation of 40 % masked entries
 
 The PEMS files are not redistributable, so the script writes a synthetic PEMS-shaped data set (distance csv,
@@ -94,6 +95,24 @@ def main():
     print(f"  CG iterations x/zu/zd of the last ADMM iteration: {blk.CG_iter_x[-1].float().mean():.1f} / "
           f"{blk.CG_iter_zu[-1].float().mean():.1f} / {blk.CG_iter_zd[-1].float().mean():.1f}; "
           f"primal residuals {['%.3g' % v for v in blk.p_res_list[-1]]}")
+
+    # the notebooks' grid search (one combined_loop per value there): 3 x 3 sets of (mu_u, mu_d1) on the first 16 windows as ONE
+    # batch of 144 samples, every sample with its own weights
+    nw = min(16, args.batch)
+    grid = {"mu_u": [0.5 * admm_info["mu_u"], admm_info["mu_u"], 2 * admm_info["mu_u"]],
+            "mu_d1": [0.5 * admm_info["mu_d1"], admm_info["mu_d1"], 2 * admm_info["mu_d1"]]}
+    blk._reset_history()
+    blk.admm_convergence = "per_sample"                           # the stop test of a sweep: every cell on its own residuals
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    xs, n_it, sets = blk.sweep(y[:nw], grid)                      # (9, nw, 24, N, 1), (9, nw), 9 dicts
+    torch.cuda.synchronize(); dt = time.perf_counter() - t0
+    blk.admm_convergence = "whole_batch"
+    truth = ds.recover_data(x_true[:nw, 12:])
+    mae = [(ds.recover_data(xs[p][:, 12:]) - truth).abs().mean().item() for p in range(len(sets))]
+    print(f"sweep: {len(sets)} sets x {nw} windows x {int(n_it.max())} ADMM iterations in {dt * 1e3:.1f} ms; MAE of the 12 predicted steps")
+    print("  mu_u \\ mu_d1 " + "".join(f"{v:>9.3g}" for v in grid["mu_d1"]))
+    for i, a in enumerate(grid["mu_u"]):
+        print(f"  {a:>13.3g} " + "".join(f"{mae[i * 3 + j]:>9.3f}" for j in range(3)))
 
     ix, iy, mask = ds.get_interpolated_batch(starts, 0.4)
     blk._reset_history()

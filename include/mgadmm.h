@@ -156,7 +156,8 @@ typedef struct mgadmm_solver mgadmm_solver;
 
 /* "mgadmm <major>.<minor>.<patch> (gfx950)".  The minor number changes whenever a struct of this header grows (0.2:
  * mgadmm_params gained cg_convergence and max_inner_iter; 0.3: mgadmm_params gained admm_convergence, mgadmm_history gained
- * n_iters_per_sample): a caller built against an older header must be rebuilt -- compare the string before passing structs. */
+ * n_iters_per_sample): a caller built against an older header must be rebuilt -- compare the string before passing structs.
+ * The patch number counts additions that leave every struct alone (0.3.1: mgadmm_solver_set_sample_params). */
 const char* mgadmm_version(void);
 const char* mgadmm_last_error(void);
 
@@ -174,6 +175,26 @@ int mgadmm_solver_create(mgadmm_graph* g, const mgadmm_params* p, int32_t max_ba
 int mgadmm_solver_destroy(mgadmm_solver* s);
 /* attribute assignment after construction (blk.max_ADMM_iter = ..., blk.rho = ...) */
 int mgadmm_solver_set_params(mgadmm_solver* s, const mgadmm_params* p);
+/* Per-sample ADMM weights: sample b of a batch solves with its own six weights of ADMM_info (a hyperparameter sweep over
+ * P sets on W windows as one batch of P * W samples, each equal to the solve run alone with those scalars, bit for bit).
+ * Host arrays of B doubles; NULL = every sample uses the scalar of mgadmm_params. */
+typedef struct {
+    const double *rho, *rho_u, *rho_d, *mu_u, *mu_d1, *mu_d2;
+} mgadmm_sample_params;
+/* Per-sample ADMM weights for the following mgadmm_solve / mgadmm_solve_from calls with this B.  sp == NULL or B == 0 clears
+ * them.  The arrays are copied.  B > max_batch, a value that is not finite, rho / rho_u / rho_d <= 0 or mu_* < 0 ->
+ * MGADMM_ERR_INVALID (the message names the field and the sample).  mgadmm_solver_set_params keeps the table; its NULL
+ * fields follow the new scalars.  While a table is set (decided when a solve starts, before anything runs):
+ *   - a solve with another B -> MGADMM_ERR_INVALID;
+ *   - LDS-resident float32 path only: a solve that would take the streaming path (MGADMM_PATH_STREAM, MGADMM_F64,
+ *     MGADMM_CG_BATCH_MAX, a graph the LDS path cannot hold) -> MGADMM_ERR_UNSUPPORTED;
+ *   - check_stop = 1 with MGADMM_ADMM_WHOLE_BATCH -> MGADMM_ERR_UNSUPPORTED (one stop test over the summed residuals of
+ *     different problems means nothing): a sweep runs a fixed count (check_stop = 0) or stops per sample
+ *     (MGADMM_ADMM_PER_SAMPLE);
+ *   - history, metrics_per_sample, n_iters_per_sample, cg_iters, cg_alpha / cg_beta are filled as without a table.
+ * mgadmm_two_loops and the fine-grained entry points (mgadmm_lhs, mgadmm_cg, mgadmm_phi_direct, mgadmm_apply) keep using
+ * the scalars of mgadmm_params. */
+int mgadmm_solver_set_sample_params(mgadmm_solver* s, const mgadmm_sample_params* sp, int32_t B);
 /* bytes of device workspace held by the solver */
 int64_t mgadmm_solver_workspace_bytes(const mgadmm_solver* s);
 /* which path (MGADMM_PATH_STREAM / MGADMM_PATH_LDS) a batch of size B would take */

@@ -46,6 +46,11 @@ int mgadmm_solver_set_params(mgadmm_solver* s, const mgadmm_params* p) {
     return s->eng->set_params(*p);
 }
 
+int mgadmm_solver_set_sample_params(mgadmm_solver* s, const mgadmm_sample_params* sp, int32_t B) {
+    MG_REQUIRE(s, "set_sample_params: null solver");
+    return s->eng->set_sample_params(sp, B);
+}
+
 int64_t mgadmm_solver_workspace_bytes(const mgadmm_solver* s) { return s ? s->eng->workspace_bytes() : 0; }
 int mgadmm_solver_path(const mgadmm_solver* s, int32_t B) { return s ? s->eng->path_for(B) : MGADMM_ERR_INVALID; }
 

@@ -102,6 +102,11 @@ struct Engine : EngineBase {
     int* d_pstop = nullptr;       // [Bp_max] stop words, [1] number of stopped samples, [Bp_max] iterations of every sample
     double* d_ps_full = nullptr;  // [max_admm_iter][NMETRIC][Bp]: per-sample metric sums of every iteration (allocated on first use)
     size_t ps_full_elems = 0;
+    // per-sample ADMM weights (mgadmm_solver_set_sample_params): the caller's arrays (empty = the scalar of `p`) and the device
+    // table of the records k_admm_lds_pp reads, rebuilt whenever the arrays or the scalars change
+    int sp_B = 0;                 // samples of the table; 0 = none set
+    std::vector<double> sp_val[6];   // rho, rho_u, rho_d, mu_u, mu_d1, mu_d2
+    LdsSampleParams* d_sp = nullptr;   // [Bmax]
     std::vector<float*> lds_ring_extra;   // iterate buffers beyond the 15 workspace vectors (chunks longer than 7 iterations)
     int64_t lds_instance = -1;       // MGADMM_Q_LDS_INSTANCE: template arguments of the k_admm_lds instance of the last launch
     int lds_chunk = LDS_MAXJ_POOL;   // MGADMM_LDS_CHUNK: ADMM iterations per k_admm_lds launch when the iteration count is fixed (1 .. LDS_MAXJ_POOL)
@@ -129,6 +134,7 @@ struct Engine : EngineBase {
         fr(vec_pool); fr(partials); fr(d_rr); fr(d_alpha); fr(d_beta); fr(d_alpha_hist); fr(d_beta_hist);
         fr(d_active); fr(d_iters_tmp); fr(d_nact); fr(d_nonfinite); fr(d_ps); fr(d_hist); fr(d_dxps);
         fr(d_dxpart); fr(d_hist_ps); fr(d_cg_iters); fr(d_lds_csr); fr(d_m2); fr(d_stop); fr(d_ps_ring); fr(d_pstop); fr(d_ps_full);
+        fr(d_sp);
         for (float* b : lds_ring_extra) if (b) (void)hipFree(b);
         if (st_side) (void)hipStreamDestroy(st_side);
         for (auto& e : ev_main) if (e) (void)hipEventDestroy(e);
@@ -533,7 +539,75 @@ struct Engine : EngineBase {
         p = np;
         sv->p = np;
         MG_HIP(hipSetDevice(g->device));
-        return alloc_iter_dependent();
+        MG_TRY(alloc_iter_dependent());
+        return sp_B > 0 ? upload_sample_params() : (int)MGADMM_OK;      // (fields that were not given follow the new scalars)
+    }
+
+    // ---------------------------------------------------------------- per-sample ADMM weights
+    int set_sample_params(const mgadmm_sample_params* sp, int B) override {
+        if (sp == nullptr || B == 0) {
+            sp_B = 0;
+            for (auto& v : sp_val) v.clear();
+            return MGADMM_OK;
+        }
+        MG_REQUIRE(B >= 1 && B <= Bmax, "set_sample_params: batch %d outside [1, max_batch=%d]", B, Bmax);
+        static const char* const names[6] = {"rho", "rho_u", "rho_d", "mu_u", "mu_d1", "mu_d2"};
+        const double* const src[6] = {sp->rho, sp->rho_u, sp->rho_d, sp->mu_u, sp->mu_d1, sp->mu_d2};
+        for (int f = 0; f < 6; ++f) {
+            if (!src[f]) continue;
+            for (int b = 0; b < B; ++b) {
+                const double v = src[f][b];
+                MG_REQUIRE(std::isfinite(v), "set_sample_params: %s[%d] is not finite", names[f], b);
+                if (f < 3) MG_REQUIRE(v > 0.0, "set_sample_params: %s[%d] = %g, should be > 0", names[f], b, v);
+                else MG_REQUIRE(v >= 0.0, "set_sample_params: %s[%d] = %g, should be >= 0", names[f], b, v);
+            }
+        }
+        for (int f = 0; f < 6; ++f) {
+            if (src[f]) sp_val[f].assign(src[f], src[f] + B);
+            else sp_val[f].clear();
+        }
+        sp_B = B;
+        MG_HIP(hipSetDevice(g->device));
+        return upload_sample_params();
+    }
+
+    // record b of the device table from sample b's six doubles: the expressions and casts solve_lds uses for the scalars
+    int upload_sample_params() {
+        std::vector<LdsSampleParams> rec((size_t)sp_B);
+        const double scalar[6] = {p.rho, p.rho_u, p.rho_d, p.mu_u, p.mu_d1, p.mu_d2};
+        for (int b = 0; b < sp_B; ++b) {
+            double w[6];
+            for (int f = 0; f < 6; ++f) w[f] = sp_val[f].empty() ? scalar[f] : sp_val[f][(size_t)b];
+            const LhsDef dx = lhs_def_of(MGADMM_LHS_X, p.ablation, w[0], w[1], w[2], w[3], w[5]);
+            LdsSampleParams& r = rec[(size_t)b];
+            r.cx1 = (float)dx.c1; r.cx2 = (float)dx.c2;
+            r.rho = (float)w[0]; r.rho_u = (float)w[1]; r.rho_d = (float)w[2];
+            r.mu_u = (float)w[3]; r.mu_d1 = (float)w[4]; r.mu_d2 = (float)w[5];
+        }
+        if (!d_sp) MG_HIP(hipMalloc(&d_sp, sizeof(LdsSampleParams) * (size_t)Bmax));
+        MG_HIP(hipMemcpy(d_sp, rec.data(), sizeof(LdsSampleParams) * rec.size(), hipMemcpyHostToDevice));
+        return MGADMM_OK;
+    }
+
+    // A solve with a table set: decided when the solve starts (table and parameters arrive in separate calls, in either
+    // order), before anything is enqueued.  The weights are read by the LDS-resident kernel only (one workgroup owns a sample).
+    int check_sample_params(int B) const {
+        MG_REQUIRE(B == sp_B, "solve: the sample_params table holds %d samples, the solve has B = %d", sp_B, B);
+        const char* why = nullptr;
+        if (!std::is_same<S, float>::value) why = "float64 arithmetic runs on the streaming path";
+        else if (p.path == MGADMM_PATH_STREAM) why = "path is MGADMM_PATH_STREAM";
+        else if (p.cg_convergence == MGADMM_CG_BATCH_MAX) why = "cg_convergence batch_max runs on the streaming path";
+        else if (!lds.ok) why = "the LDS-resident path cannot hold this graph (it needs T*N*8 B + tables <= 160 KiB and N*G <= 1024)";
+        if (why) {
+            mg_set_error("solve: sample_params (per-sample ADMM weights) are implemented by the LDS-resident float32 path only: %s", why);
+            return MGADMM_ERR_UNSUPPORTED;
+        }
+        if (p.check_stop && p.admm_convergence == MGADMM_ADMM_WHOLE_BATCH) {
+            mg_set_error("solve: sample_params with check_stop need admm_convergence per_sample (the whole_batch stop test would sum "
+                         "the residuals of different problems); or run a fixed count with check_stop = 0");
+            return MGADMM_ERR_UNSUPPORTED;
+        }
+        return MGADMM_OK;
     }
 
     int64_t workspace_bytes() const override { return ws_bytes; }
@@ -800,14 +874,15 @@ struct Engine : EngineBase {
         return MGADMM_OK;
     }
 
-    LhsDef lhs_def(int which) const {
+    LhsDef lhs_def(int which) const { return lhs_def_of(which, p.ablation, p.rho, p.rho_u, p.rho_d, p.mu_u, p.mu_d2); }
+    static LhsDef lhs_def_of(int which, int ablation, double rho, double rho_u, double rho_d, double mu_u, double mu_d2) {
         switch (which) {
             case MGADMM_LHS_X:
-                if (p.ablation == MGADMM_ABL_NONE) return {1, 1, (p.rho_u + p.rho_d) / 2, p.rho / 2};
-                if (p.ablation == MGADMM_ABL_DGLR) return {1, 1, p.rho_u / 2, p.rho / 2};
-                return {0, 1, (p.rho_u + p.rho_d) / 2, 0.0};
-            case MGADMM_LHS_ZU: return {2, 0, p.rho_u / 2, p.mu_u};
-            default: return {1, 0, p.rho_d / 2, p.mu_d2};
+                if (ablation == MGADMM_ABL_NONE) return {1, 1, (rho_u + rho_d) / 2, rho / 2};
+                if (ablation == MGADMM_ABL_DGLR) return {1, 1, rho_u / 2, rho / 2};
+                return {0, 1, (rho_u + rho_d) / 2, 0.0};
+            case MGADMM_LHS_ZU: return {2, 0, rho_u / 2, mu_u};
+            default: return {1, 0, rho_d / 2, mu_d2};
         }
     }
 
@@ -1112,6 +1187,7 @@ struct Engine : EngineBase {
         MG_REQUIRE(y && x_out, "solve: null pointer");
         if (state_in) MG_TRY(check_state_in(x0, state_in));
         st = s;
+        if (sp_B > 0) MG_TRY(check_sample_params(B));
         if (p.path == MGADMM_PATH_LDS && !lds.ok) {
             mg_set_error("solve: the LDS-resident path needs float32, T*N*8 B + CSR <= 160 KiB and N*G <= 1024 (N=%d, T=%d)", N, T);
             return MGADMM_ERR_UNSUPPORTED;
@@ -1762,6 +1838,7 @@ struct Engine : EngineBase {
             if (ps_mode) {
                 a.pstop = d_pstop; a.pstop_count = d_pcount; a.x_final = xo_; a.admm_tol = p.admm_tol;
             }
+            if (sp_B > 0) a.sp = d_sp;        // (B == sp_B: check_sample_params) the launches take the kernels k_admm_lds_pp
             // number of stopped samples after launch `c`, read LAG launches late: true when every sample has stopped
             auto all_stopped = [&](int c, bool* done) -> int {
                 MG_HIP(hipMemcpyAsync(h_flag + 1 + c % (LAG + 1), d_pcount, sizeof(int), hipMemcpyDeviceToHost, st));

@@ -46,6 +46,12 @@ struct LdsArgsCore {
     const int* stop;       // device stop word of the ADMM outer loop (nullptr: none): a launch enqueued speculatively after the
                            // stop test of an earlier iteration passed returns at its first instruction
 };
+// Per-sample ADMM weights (mgadmm_solver_set_sample_params): one record per workgroup launched, the eight values a trip of
+// k_admm_lds reads from LdsArgsCore, formed by the host from sample b's six doubles with the expressions of the scalars
+struct LdsSampleParams {
+    float rho, rho_u, rho_d, mu_u, mu_d1, mu_d2;
+    float cx1, cx2;
+};
 struct LdsArgs : LdsArgsCore {
     float* xs[LDS_MAXJ + 1];   // trip k reads the iterate xs[k] and writes xs[k + 1] (every iterate is kept: delta_x_per_step);
                                // indexed by the trip number straight from the kernarg segment
@@ -57,6 +63,10 @@ struct LdsArgs : LdsArgsCore {
     float* x_final;        // (B, TN): a sample that stops stores its iterate here itself (the iterate buffers of a chunk rotate)
     double admm_tol;       // ADMM_tol
     int it0;               // number of the launch's first iteration in this solve (n_b = it0 + trip + 1)
+    // Per-sample weights (read by the kernels k_admm_lds_pp only, which a launch takes when sp != nullptr; behind everything the
+    // other kernels read): workgroup b takes rho .. cx2 from sp[b] instead of the scalars above.  In these kernels the
+    // per-sample stop test runs when pstop != nullptr
+    const LdsSampleParams* sp;   // [B] device table
 };
 
 // Execution plan of k_admm_lds chosen by Engine::plan_lds
@@ -76,6 +86,8 @@ struct LdsLaunch {
 int mg_lds_iteration(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t st);
 // the same with the per-sample stop test (a.pstop != nullptr; mg_lds_iteration forwards to it)
 int mg_lds_iteration_ps(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t st);
+// the same with per-sample weights (a.sp != nullptr; mg_lds_iteration forwards to it), with or without the stop test
+int mg_lds_iteration_pp(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t st);
 // initial state (ADMM.py:528-544): x in the reference's sample-major layout, zu / zd / gamma* thread-major for time groups of TPG steps
 int mg_lds_init(bool masked, int T, int t_in, int N, int TPG, int B, float tm, float den, const float* y, const float* mask, float* x,
                 float* zu, float* zd, float* gam, float* gu, float* gd, int* nonfinite, hipStream_t st);

@@ -779,12 +779,33 @@ __device__ __forceinline__ int lds_cg(LdsCtx<TPG, BAND, NU, ND, TP>& c, BlockRed
 // (lds_launch.hip) are compiled from the very code they had before the mode existed and keep their names -- their register
 // allocation is fragile (profiles/r04/kernel_registers.txt: moving the body into a function shared by two kernels already
 // changed the spill counts of 30 of them); the instances with the test are the kernels k_admm_lds_ps of lds_launch_ps.hip.
+// PP (MGADMM_LDS_PER_SAMPLE_PARAMS, defined by lds_launch_pp.hip): per-sample ADMM weights (mgadmm_solver_set_sample_params) --
+// the eight weights a trip reads (rho, rho_u, rho_d, cx1, cx2, mu_u, mu_d2, mu_d1) come from record b of the table
+// LdsArgs::sp instead of the kernel arguments: MG_LDS_W(field), a workgroup-uniform load through the constant address space
+// (a scalar load, so the values stay in scalar registers as the arguments did; the table does not change while a launch
+// runs).  The same arithmetic in the same order otherwise.  The stop test of PS is compiled into these kernels too and runs
+// when the launch carries stop words (MG_LDS_PSTOP_ON): a sweep runs a fixed count or stops per sample.  Again a flag of the
+// translation unit: the kernels k_admm_lds_pp of lds_launch_pp.hip; in the other two units both macros expand to what the
+// source said before them.
+#ifdef MGADMM_LDS_PER_SAMPLE_PARAMS
+#define MG_LDS_KERNEL k_admm_lds_pp
+#define MG_LDS_PS true
+#define MG_LDS_PSTOP_ON(args) ((args).pstop != nullptr)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MG_LDS_W(field) (((const LdsSampleParams __attribute__((address_space(4)))*)a.sp)[b].field)
+#else
+#define MG_LDS_W(field) (a.sp[b].field)
+#endif
+#else
 #ifdef MGADMM_LDS_PER_SAMPLE_STOP
 #define MG_LDS_KERNEL k_admm_lds_ps
 #define MG_LDS_PS true
 #else
 #define MG_LDS_KERNEL k_admm_lds
 #define MG_LDS_PS false
+#endif
+#define MG_LDS_PSTOP_ON(args) true
+#define MG_LDS_W(field) (a.field)
 #endif
 template <int TPG, bool BAND, int MAXT, bool SB, int NU = 0, int ND = 0, bool SLOTS = false, int TP = -1>
 __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERNEL(LdsArgs a_in) {
@@ -807,7 +828,7 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
     // that follows the stopping iteration must leave the state alone (workgroup-uniform scalar load)
     if (a_in.stop != nullptr && *a_in.stop != 0) return;
     if constexpr (PS) {       // this sample stopped in an earlier launch: its state and x_out[b] are final (workgroup-uniform scalar load)
-        if (a_in.pstop[b] != 0) return;
+        if (MG_LDS_PSTOP_ON(a_in) && a_in.pstop[b] != 0) return;
     }
     // STAGGERED START.  Samples of one batch need (nearly) the same CG iteration counts, so the workgroups of a launch
     // run in lock step: all CUs store their results and request the next sample's operands at the same moment, while HBM
@@ -943,7 +964,7 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
     const int ty = a.mask ? a.T : a.t_in;
     const float* yb = a.y + (size_t)b * ty * a.N;
     const bool has_phi = a.has_phi, has_zd = a.has_zd;
-    const float rho = a.rho, rho_u = a.rho_u, rho_d = a.rho_d;
+    const float rho = MG_LDS_W(rho), rho_u = MG_LDS_W(rho_u), rho_d = MG_LDS_W(rho_d);
     const int Nn = a.N;
 
     // REQUEST of two operand vectors (TPG elements each per thread): 2 * TPG unconditional loads issued together and
@@ -1110,7 +1131,7 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
     // ---- x solve (ADMM.py:571)
     int itx;
     {
-        float cx1 = a.cx1, cx2 = a.cx2;
+        float cx1 = MG_LDS_W(cx1), cx2 = MG_LDS_W(cx2);
         int t_in = a.t_in;
         MG_PIN_S(cx1); MG_PIN_S(cx2); MG_PIN_S(t_in);
         if (a.lhsx_kind == 1) itx = lds_cg<TPG, BAND, 1, SB, NU, ND, TP>(c, br, x, rhs, mk, 1, t_in, cx1, cx2, max_cg, tol, ah, bh, Bp, nonfinite, R);
@@ -1170,7 +1191,7 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
     // ---- zu solve + gamma_u update (ADMM.py:579-580, 595)
     int itzu;
     {
-        float c1 = rho_u * 0.5f, c2 = a.mu_u;
+        float c1 = rho_u * 0.5f, c2 = MG_LDS_W(mu_u);
         MG_PIN_V(c1); MG_PIN_S(c2);
         itzu = lds_cg<TPG, BAND, 2, SB, NU, ND, TP>(c, br, z, rhs, nullptr, 0, 0, c1, c2, max_cg, tol, ah ? ah + hstride : nullptr,
                                                  bh ? bh + hstride : nullptr, Bp, nonfinite, R);
@@ -1226,7 +1247,7 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
             rhs[k] = gn[k] * 0.5f + rho_d * 0.5f * xr[k];
         }
         {
-            float c1 = rho_d * 0.5f, c2 = a.mu_d2;
+            float c1 = rho_d * 0.5f, c2 = MG_LDS_W(mu_d2);
             MG_PIN_V(c1); MG_PIN_S(c2);
             itzd = lds_cg<TPG, BAND, 1, SB, NU, ND, TP>(c, br, z, rhs, nullptr, 0, 0, c1, c2, max_cg, tol, ah ? ah + 2 * hstride : nullptr,
                                                      bh ? bh + 2 * hstride : nullptr, Bp, nonfinite, R);
@@ -1292,7 +1313,7 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
     {
         float l[TPG];
         c.op_ldr(P, xr, l, R);
-        const float thr = a.mu_d1 / rho;
+        const float thr = MG_LDS_W(mu_d1) / rho;
         float pn[TPG], gnew[TPG];
 #pragma unroll
         for (int k = 0; k < TPG; ++k) {
@@ -1362,7 +1383,7 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
         cgi[a.Bp + b] = itzu;
         cgi[2 * a.Bp + b] = itzd;
     }
-    if constexpr (PS) {
+    if constexpr (PS) if (MG_LDS_PSTOP_ON(a)) {
         // PER-SAMPLE STOP TEST (ADMM.py:645-646 on a batch of one).  Every thread forms the residual sums of the sample from the
         // wave totals in LDS (broadcast reads; the association of the sums stored to `ps` above: the same doubles) and takes the
         // square roots and comparisons of k_batch_metrics + k_lds_stop_test at B = 1 -- the decision is workgroup-uniform

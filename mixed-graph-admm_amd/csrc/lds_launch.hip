@@ -2,7 +2,9 @@
 #include "lds_dispatch.h"
 
 int mg_lds_iteration(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t st) {
-    // a launch that carries per-sample stop words takes the instances with the stop test (lds_launch_ps.hip)
+    // a launch that carries per-sample weights takes the instances that read them (lds_launch_pp.hip),
+    // a launch that carries per-sample stop words the instances with the stop test (lds_launch_ps.hip)
+    if (a.sp != nullptr) return mg_lds_iteration_pp(L, a, B, st);
     return a.pstop != nullptr ? mg_lds_iteration_ps(L, a, B, st) : lds_dispatch(L, a, B, st);
 }
 

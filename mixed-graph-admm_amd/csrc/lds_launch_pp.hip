@@ -1,0 +1,7 @@
+// LDS-resident fused ADMM path: the k_admm_lds instances with per-sample ADMM weights (mgadmm_solver_set_sample_params), as
+// kernels k_admm_lds_pp.  The per-sample stop test is compiled in as well and runs when the launch carries stop words.  Own
+// translation unit: it compiles beside lds_launch.hip and lds_launch_ps.hip, whose instances stay what they were.
+#define MGADMM_LDS_PER_SAMPLE_PARAMS 1
+#include "lds_dispatch.h"
+
+int mg_lds_iteration_pp(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t st) { return lds_dispatch(L, a, B, st); }

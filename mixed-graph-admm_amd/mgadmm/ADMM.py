@@ -11,7 +11,9 @@ Batched semantics: B samples are B independent reference runs (per-sample CG con
 reference itself cannot run B > 1, ADMM.py:362).  Whole-batch residual norms are the Frobenius norms
 over the batch tensor like ADMM.py:612-636.
 """
+import contextlib
 import ctypes as C
+import itertools
 import math
 
 import numpy as np
@@ -41,6 +43,33 @@ def _stream_ptr(dev):
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+SAMPLE_PARAM_NAMES = ("rho", "rho_u", "rho_d", "mu_u", "mu_d1", "mu_d2")
+
+
+def _check_sample_params(sample_params, B):
+    """``sample_params`` of ``solve``: dict name -> 1-D sequence / tensor of length B, as a dict name -> float64 array.
+    Raises ValueError for an unknown name, a wrong length, a value that is not finite, rho* <= 0 or mu* < 0 (what
+    ``mgadmm_solver_set_sample_params`` refuses, found before the library is touched)."""
+    if not hasattr(sample_params, "items"):
+        raise ValueError(f"sample_params must be a dict with keys out of {SAMPLE_PARAM_NAMES}, got {type(sample_params).__name__}")
+    out = {}
+    for name, vals in sample_params.items():
+        if name not in SAMPLE_PARAM_NAMES:
+            raise ValueError(f"sample_params: unknown key {name!r} (expected some of {SAMPLE_PARAM_NAMES})")
+        v = vals.detach().cpu().numpy() if torch.is_tensor(vals) else np.asarray(vals)
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.ndim != 1 or v.shape[0] != B:
+            raise ValueError(f"sample_params[{name!r}] must be 1-D of length B = {B}, got shape {tuple(v.shape)}")
+        if not np.isfinite(v).all():
+            raise ValueError(f"sample_params[{name!r}][{int(np.nonzero(~np.isfinite(v))[0][0])}] is not finite")
+        bad = np.nonzero(v <= 0 if name.startswith("rho") else v < 0)[0]
+        if bad.size:
+            raise ValueError(f"sample_params[{name!r}][{int(bad[0])}] = {v[bad[0]]}: "
+                             + ("rho, rho_u and rho_d must be > 0" if name.startswith("rho") else "mu_u, mu_d1 and mu_d2 must be >= 0"))
+        out[name] = v
+    return out
 
 
 class ADMM_algorithm():
@@ -279,6 +308,22 @@ class ADMM_algorithm():
         self._solvers[(Cn, dtype)] = [h, int(B)]
         return h, p
 
+    @contextlib.contextmanager
+    def _sample_table(self, h, sp, B):
+        """Per-sample ADMM weights (``_check_sample_params`` output) set on solver ``h`` for the solves inside the block and
+        cleared after it: the next solve of the instance is an ordinary one."""
+        if not sp:
+            yield
+            return
+        spc = _lib.SampleParams()
+        for nm, v in sp.items():
+            setattr(spc, nm, v.ctypes.data_as(C.POINTER(C.c_double)))
+        _lib.check(_lib.lib.mgadmm_solver_set_sample_params(h, C.byref(spc), B))
+        try:
+            yield
+        finally:
+            _lib.lib.mgadmm_solver_set_sample_params(h, None, 0)
+
     def _dtype_for(self, t):
         if self.compute_dtype == 'match':
             if t.dtype not in _TORCH2MG:
@@ -437,13 +482,19 @@ class ADMM_algorithm():
         return None
 
     def solve(self, y, mask=None, differential=False, print_info=False, return_state=True, per_sample_history=False,
-              warm_start=None):
+              warm_start=None, sample_params=None):
         """Run the ADMM loop and return ``(x, (zu, zd), phi, history)``; ``history`` is a dict with the
         same lists that are also stored on the instance (p_res_list, d_res_list, ...).
 
         ``warm_start``: a state dict as left in ``self.state`` by a previous ``solve`` (keys x, zu, gamma_u and, as the
         ablation requires, zd, gamma_d, phi, gamma): the loop resumes from it instead of the initial guess
-        (checkpoint / resume; k1 + k2 iterations in two calls equal k1 + k2 iterations in one)."""
+        (checkpoint / resume; k1 + k2 iterations in two calls equal k1 + k2 iterations in one).
+
+        ``sample_params``: per-sample ADMM weights -- a dict with any of rho, rho_u, rho_d, mu_u, mu_d1, mu_d2, each a 1-D
+        sequence / tensor of length B (a name that is missing uses the instance's scalar): sample b solves with its own
+        weights and equals the B = 1 solve of an instance carrying them, bit for bit.  For this call only.  LDS-resident
+        float32 path only; with ``check_stop`` it needs ``admm_convergence='per_sample'`` (see ``sweep``)."""
+        sp = _check_sample_params(sample_params, y.shape[0]) if sample_params is not None else None
         if differential:
             assert mask is None, 'differential mode does not support mask'   # flag has no other effect (Q3)
         dt = self._dtype_for(y)
@@ -493,22 +544,23 @@ class ADMM_algorithm():
             be = np.full((I, 3, K, B), np.nan, dtype=np.float64)
             hs.cg_alpha = al.ctypes.data_as(C.POINTER(C.c_double))
             hs.cg_beta = be.ctypes.data_as(C.POINTER(C.c_double))
-        if warm_start is None:
-            rc = _lib.lib.mgadmm_solve(h, _ptr(yd), _ptr(md), mask_f32, B, _ptr(x), C.byref(st), C.byref(hs),
-                                       _stream_ptr(dev))
-        else:
-            need = ["x", "zu", "gamma_u"] + (["zd", "gamma_d"] if has_zd else []) + (["phi", "gamma"] if has_phi else [])
-            missing = [k2 for k2 in need if warm_start.get(k2) is None]
-            if missing:
-                raise ValueError(f"warm_start misses {missing} (ablation {self.ablation!r})")
-            win = {k2: self._dev_tensor(warm_start[k2], dt, "warm_start." + k2, self.T) for k2 in need}
-            if any(tuple(v.shape) != tuple(x.shape) for v in win.values()):
-                raise ValueError("warm_start tensors must have the shape of x (B, T, N, C)")
-            sin = _lib.State()
-            for nm in need[1:]:
-                setattr(sin, nm, win[nm].data_ptr())
-            rc = _lib.lib.mgadmm_solve_from(h, _ptr(yd), _ptr(md), mask_f32, B, _ptr(win["x"]), C.byref(sin), _ptr(x),
-                                            C.byref(st), C.byref(hs), _stream_ptr(dev))
+        with self._sample_table(h, sp, B):
+            if warm_start is None:
+                rc = _lib.lib.mgadmm_solve(h, _ptr(yd), _ptr(md), mask_f32, B, _ptr(x), C.byref(st), C.byref(hs),
+                                           _stream_ptr(dev))
+            else:
+                need = ["x", "zu", "gamma_u"] + (["zd", "gamma_d"] if has_zd else []) + (["phi", "gamma"] if has_phi else [])
+                missing = [k2 for k2 in need if warm_start.get(k2) is None]
+                if missing:
+                    raise ValueError(f"warm_start misses {missing} (ablation {self.ablation!r})")
+                win = {k2: self._dev_tensor(warm_start[k2], dt, "warm_start." + k2, self.T) for k2 in need}
+                if any(tuple(v.shape) != tuple(x.shape) for v in win.values()):
+                    raise ValueError("warm_start tensors must have the shape of x (B, T, N, C)")
+                sin = _lib.State()
+                for nm in need[1:]:
+                    setattr(sin, nm, win[nm].data_ptr())
+                rc = _lib.lib.mgadmm_solve_from(h, _ptr(yd), _ptr(md), mask_f32, B, _ptr(win["x"]), C.byref(sin), _ptr(x),
+                                                C.byref(st), C.byref(hs), _stream_ptr(dev))
         n = hs.n_iters
         self.n_iters_per_sample = nps
         if dxps is not None:
@@ -537,10 +589,41 @@ class ADMM_algorithm():
         self.state["x"] = xo
         return xo, (zu, zd), phi, self.history()
 
-    def combined_loop(self, y, mask=None, differential=False, print_info=True):
+    def combined_loop(self, y, mask=None, differential=False, print_info=True, sample_params=None):
         """``y`` (B, t_in, N, C) [or (B, T, N, C) with ``mask``] -> ``x`` (B, T, N, C), dtype/device of y.
-        History attributes are filled like the reference's (ADMM.py:612-643)."""
-        return self.solve(y, mask=mask, differential=differential, print_info=print_info, return_state=False)[0]
+        History attributes are filled like the reference's (ADMM.py:612-643).  ``sample_params``: see ``solve``."""
+        return self.solve(y, mask=mask, differential=differential, print_info=print_info, return_state=False,
+                          sample_params=sample_params)[0]
+
+    def sweep(self, y, grid, mask=None, chunk=None, **solve_kw):
+        """A grid search over ADMM weights as one batch (the reference's notebooks run one ``combined_loop`` per value).
+        ``y``: W windows; ``grid``: dict name -> list of values.  The Cartesian product of the lists (P sets, in
+        ``itertools.product`` order of the dict's key order) times the W windows is solved as a batch of P * W samples,
+        window index fastest -- in consecutive pieces of at most ``chunk`` samples when ``chunk`` is given.  Returns
+        ``(x, n_iters, sets)``: x of shape (P, W, T, N, C), n_iters (P, W) int32 (the iterations of every cell: they differ
+        with ``admm_convergence='per_sample'``), ``sets`` the list of the P dicts.  Cell (p, w) equals the B = 1 solve of
+        window w by an instance carrying ``sets[p]``.  With ``check_stop`` the instance needs
+        ``admm_convergence='per_sample'``; without it every cell runs ``max_ADMM_iter`` iterations."""
+        names = list(grid)
+        for nm in names:
+            if nm not in SAMPLE_PARAM_NAMES:
+                raise ValueError(f"sweep: unknown key {nm!r} (expected some of {SAMPLE_PARAM_NAMES})")
+        sets = [dict(zip(names, vals)) for vals in itertools.product(*[list(grid[nm]) for nm in names])]
+        W, P = y.shape[0], len(sets)
+        total = P * W
+        step = total if chunk is None else int(chunk)
+        if step < 1:
+            raise ValueError(f"sweep: chunk must be >= 1, got {chunk}")
+        solve_kw.setdefault("return_state", False)
+        xs, ns = [], []
+        for s0 in range(0, total, step):
+            s = np.arange(s0, min(total, s0 + step))             # sample s = set s // W on window s % W
+            w = torch.from_numpy(s % W)
+            sp = {nm: [float(sets[j // W][nm]) for j in s] for nm in names}
+            xs.append(self.solve(y[w], mask=None if mask is None else mask[w], sample_params=sp, **solve_kw)[0])
+            ns.append(np.array(self.n_iters_per_sample, dtype=np.int32))
+        x = torch.cat(xs, 0)
+        return x.reshape((P, W) + tuple(x.shape[1:])), np.concatenate(ns).reshape(P, W), sets
 
     def history(self):
         keys = ("p_res_list", "d_res_list", "x_shift_list", "delta_x_per_step", "GLR_list", "DGTV_list", "DGLR_list",

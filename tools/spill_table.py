@@ -9,7 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mixed-graph-admm_amd", "csrc")
 FLAGS = ["-O3", "-fno-strict-aliasing", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-I" + os.path.join(ROOT, "include"),
          "--cuda-device-only", "-S"]
-TUS = {"lds_launch.hip": ["-fno-slp-vectorize"], "lds_launch_ps.hip": ["-fno-slp-vectorize"], "solver_f32.hip": [], "solver_f64.hip": [], "graph.hip": [], "build.hip": [], "frontend.hip": []}
+TUS = {"lds_launch.hip": ["-fno-slp-vectorize"], "lds_launch_ps.hip": ["-fno-slp-vectorize"], "lds_launch_pp.hip": ["-fno-slp-vectorize"], "solver_f32.hip": [], "solver_f64.hip": [], "graph.hip": [], "build.hip": [], "frontend.hip": []}
 
 
 def demangle(names):
