@@ -15,6 +15,7 @@
 #include "stream_kernels.h"
 #include "lds_args.h"
 #include "lds_banks.h"
+#include "lds_rows.h"
 
 namespace {
 
@@ -89,6 +90,9 @@ struct Engine : EngineBase {
         int G = 0, TPG = 0, TS = 0, nthreads = 0, block = 0, NR = 0, csr_ints = 0, maxt = 1024, sb = 0, uniform45 = 0, slots = 0;
         int tail_pairs = 0, lds_img0 = 0, lds_img_ints = 0;
         int off_rp_u = 0, off_rp_d = 0, off_en_u = 0, off_en_d = 0, off_lead_t = 0, off_tail_t = 0, off_diag = 0;
+        int row_order = 0;            // ldsrows::Order of the thread -> row map (lds_rows.h); 0: node order
+        int off_node = 0, off_rown = 0;   // node_of_row [NR] / row_of_node [N] in the global image
+        uint64_t npos_word = 0;       // table positions per wave, 4-bit fields (LdsArgs::npos)
         size_t lds_bytes = 0;
     } lds;
     int* d_lds_csr = nullptr;
@@ -1533,16 +1537,37 @@ struct Engine : EngineBase {
             }
             return o;
         };
-        const HostCsr hWdT_off = band ? HostCsr() : strip_diag(g->hWdT, diag_t);
         // W_d^T: LDS_NLEAD leading entries per row + a tail table of 2 * tail_pairs entries per row (rows padded with
-        // {own row, weight 0}): one trip count for every lane of the workgroup
-        int maxlen_t = 0;
+        // {own row, weight 0}): one table width for every lane of the workgroup
+        std::vector<int> deg_t(N, 0);                         // off-diagonal in-degree of W_d = length of a W_d^T row
         if (!band)
-            for (int i = 0; i < N; ++i) maxlen_t = std::max(maxlen_t, hWdT_off.rowptr[i + 1] - hWdT_off.rowptr[i]);
+            for (int i = 0; i < N; ++i)
+                for (int e = g->hWdT.rowptr[i]; e < g->hWdT.rowptr[i + 1]; ++e) deg_t[i] += g->hWdT.col[e] != i;
+        const int maxlen_t = N > 0 ? *std::max_element(deg_t.begin(), deg_t.end()) : 0;
         const int tp = band ? 0 : (std::max(0, maxlen_t - LDS_NLEAD) + 1) / 2;
         const int WT = LDS_NLEAD + 2 * tp;
         lds.tail_pairs = tp;
-        const HostCsr hWd_tab = band ? HostCsr() : (lds.uniform45 ? strip_diag(g->hWd, diag_d) : g->hWd);
+        // ROW PLAN (lds_rows.h) of the uniform-row instances with a compile-time tail (tail_pairs <= 3, lds_dispatch.h): the rows
+        // that need tail pairs are owned by the first threads of every time group, so that most waves hold rows that fit the
+        // leading entries and gather no tail pair at all (a wave gathers as many table positions as its longest row holds).
+        // From here on this function works on the relabelled graph (row numbers); node numbers stay in the HBM-facing indices
+        // (node_of_row for k_admm_lds, row_of_node for k_init_lds / k_state_layout).
+        // MGADMM_LDS_ROW_ORDER: 2 (default) = by tail pairs needed, node order inside a class; 1 = by in-degree (fewest positions,
+        // but the neighbours of consecutive lanes are scattered: the bank conflicts of all three gathers cost more than the
+        // positions save); 0 = node order and full counts (the A/B leg).  The other instances: always node order.
+        const char* ro_env = getenv("MGADMM_LDS_ROW_ORDER");
+        lds.row_order = (lds.uniform45 && tp <= 3) ? (ro_env ? std::max(0, std::min(atoi(ro_env), 2)) : (int)ldsrows::TAIL_CLASS) : 0;
+        const ldsrows::Plan rows = ldsrows::make_plan(deg_t, lds.G, WT, lds.row_order, LDS_NLEAD);
+        lds.npos_word = 0;
+        if (lds.uniform45 && tp <= 3 && !ldsrows::pack_npos(rows, &lds.npos_word)) {
+            mg_set_error("lds: row plan does not fit its launch word (%d waves)", (int)rows.npos.size());
+            return MGADMM_ERR_INVALID;
+        }
+        const HostCsr Wu = lds.row_order ? ldsrows::relabel(g->hWu, rows) : g->hWu;
+        const HostCsr Wd = lds.row_order ? ldsrows::relabel(g->hWd, rows) : g->hWd;
+        const HostCsr WdT = lds.row_order ? ldsrows::relabel(g->hWdT, rows) : g->hWdT;
+        const HostCsr hWdT_off = band ? HostCsr() : strip_diag(WdT, diag_t);
+        const HostCsr hWd_tab = band ? HostCsr() : (lds.uniform45 ? strip_diag(Wd, diag_d) : Wd);
         // host tables with the ghosts' rows appended
         auto with_ghosts = [&](const HostCsr& h, int fixed_len) {
             HostCsr o;
@@ -1554,7 +1579,7 @@ struct Engine : EngineBase {
             }
             return o;
         };
-        const HostCsr hu = with_ghosts(g->hWu, lds.uniform45 ? 4 : 0);
+        const HostCsr hu = with_ghosts(Wu, lds.uniform45 ? 4 : 0);
         const HostCsr hd = band ? HostCsr() : with_ghosts(hWd_tab, lds.uniform45 ? 4 : 0);
         const int nu = hu.nnz(), nd = band ? 0 : hd.nnz();
         auto al4 = [](int v) { return (v + 3) & ~3; };
@@ -1570,6 +1595,8 @@ struct Engine : EngineBase {
         const int tail_ints = off - lds.off_tail_t;
         lds.off_diag = off; off += 2 * NR;
         off += 8;                                            // the paired loops of the ragged gathers read three entries ahead
+        lds.off_node = off; off += NR;                       // node_of_row (ghost rows: 0), read by k_admm_lds once per trip
+        lds.off_rown = off; off += N;                        // row_of_node, read by k_init_lds / k_state_layout
         lds.csr_ints = off;
         lds.lds_img0 = lds.uniform45 ? lds.off_tail_t : 0;
         lds.lds_img_ints = lds.uniform45 ? tail_ints : lds.off_diag;
@@ -1639,24 +1666,19 @@ struct Engine : EngineBase {
             put_csr(hd, lds.off_rp_d, lds.off_en_d, fixed_or_pairs);
             // W_d^T as a table of WT entries per row: the row's entries, then {own row, 0}; every lane reads every position
             // (FIXED stream of the bank model), the first LDS_NLEAD positions from registers, the others from the tail table
-            HostCsr ht;
-            ht.rowptr.push_back(0);
-            std::vector<int> from;                            // index into hWdT, -1: padding
-            for (int i = 0; i < N; ++i) {
-                const int e0 = hWdT_off.rowptr[i], len = hWdT_off.rowptr[i + 1] - e0;
-                for (int e = 0; e < WT; ++e) {
-                    ht.col.push_back(e < len ? hWdT_off.col[e0 + e] : i);
-                    ht.val.push_back(e < len ? hWdT_off.val[e0 + e] : 0.f);
-                    from.push_back(e < len ? e0 + e : -1);
-                }
-                ht.rowptr.push_back((int)ht.col.size());
-            }
-            const std::vector<int> order = slot_order(ht, ldsbank::FIXED);
+            // With a row plan the entries of row r sit in the positions below lim[r] (what every wave that owns the row gathers).
+            ldsbank::Geometry q;
+            q.N = N; q.G = T / best; q.TPG = best; q.TS = lds.TS; q.nlead = LDS_NLEAD;
+            ldsbank::Result sr;
+            const ldsrows::Table ht = ldsrows::build_table(q, hWdT_off.rowptr, hWdT_off.col, hWdT_off.val, rows, WT, bank_order, search_steps, &sr);
+            if (bank_order && search_steps > 0 && getenv("MGADMM_LDS_BANK_STATS"))
+                fprintf(stderr, "[mgadmm] lds bank search: W_d^T table, %d entries: %.0f -> %.0f conflict cycles per application (%ld steps)\n",
+                        hWdT_off.rowptr[N], sr.before, sr.after, sr.moves);
             for (int r = 0; r < NR; ++r)
                 for (int e = 0; e < WT; ++e) {
                     const int at = e < LDS_NLEAD ? lds.off_lead_t + 2 * (r * LDS_NLEAD + e)
                                                  : lds.off_tail_t + 2 * (r * 2 * tp + (e - LDS_NLEAD));
-                    if (r < N) put_entry(at, ht.col[order[r * WT + e]], ht.val[order[r * WT + e]]);
+                    if (r < N) put_entry(at, ht.col[(size_t)r * WT + e], ht.val[(size_t)r * WT + e]);
                     else put_entry(at, r, 0.f);
                 }
             put_entry(lds.off_tail_t + 2 * NR * 2 * tp, 0, 0.f);
@@ -1664,6 +1686,7 @@ struct Engine : EngineBase {
             memcpy(&img[lds.off_diag], diag_d.data(), sizeof(float) * NR);
             memcpy(&img[lds.off_diag + NR], diag_t.data(), sizeof(float) * NR);
         }
+        for (int r = 0; r < N; ++r) { img[lds.off_node + r] = rows.node_of_row[r]; img[lds.off_rown + r] = rows.row_of_node[r]; }
         MG_HIP(hipMalloc(&d_lds_csr, sizeof(int) * off));
         MG_HIP(hipMemcpy(d_lds_csr, img.data(), sizeof(int) * off, hipMemcpyHostToDevice));
         MG_HIP(hipMalloc(&d_m2, sizeof(double) * T * N * (1 + (size_t)(Bmax + 63) / 64)));
@@ -1685,6 +1708,9 @@ struct Engine : EngineBase {
         lds.ok = true;
         return MGADMM_OK;
     }
+
+    // row_of_node on the device for the kernels that convert between node order and the thread-major state (nullptr: identity)
+    const int* lds_row_of_node() const { return lds.row_order ? d_lds_csr + lds.off_rown : nullptr; }
 
     int launch_lds(const LdsArgs& a, int B) {
         const bool timed = prof_open(0, 0.0);
@@ -1785,7 +1811,7 @@ struct Engine : EngineBase {
                 const size_t nb = (size_t)B * TN * sizeof(float);
                 if (x0 != nullptr && xbuf(0) != x0) MG_HIP(hipMemcpyAsync(xbuf(0), x0, nb, hipMemcpyDeviceToDevice, st));
                 auto in = [&](float* dst, const void* src) {
-                    return src == nullptr ? (int)MGADMM_OK : mg_lds_state_layout(true, T, N, lds.TPG, B, (const float*)src, dst, st);
+                    return src == nullptr ? (int)MGADMM_OK : mg_lds_state_layout(true, T, N, lds.TPG, B, (const float*)src, dst, lds_row_of_node(), st);
                 };
                 MG_TRY(in(zu, state_in->zu));
                 MG_TRY(in(gu, state_in->gamma_u));
@@ -1800,7 +1826,7 @@ struct Engine : EngineBase {
                 t2m /= (float)p.t_in;
                 const float den = t2m - tm * tm;
                 MG_TRY(mg_lds_init(mask != nullptr, T, p.t_in, N, lds.TPG, B, tm, den, (const float*)y, (const float*)mask, xbuf(0), zu, zd, gam, gu, gd,
-                                   d_nonfinite, st));
+                                   d_nonfinite, lds_row_of_node(), st));
             }
             LdsArgs a{};
             a.T = T; a.N = N; a.TN = (int)TN; a.TS = lds.TS; a.t_in = p.t_in; a.G = lds.G; a.B = B; a.Bp = Bp;
@@ -1818,6 +1844,7 @@ struct Engine : EngineBase {
             a.csr = d_lds_csr; a.lds_img0 = lds.lds_img0; a.lds_img_ints = lds.lds_img_ints;
             a.off_rp_u = lds.off_rp_u; a.off_rp_d = lds.off_rp_d;
             a.off_en_u = lds.off_en_u; a.off_en_d = lds.off_en_d; a.off_lead_t = lds.off_lead_t; a.off_tail_t = lds.off_tail_t; a.off_diag = lds.off_diag;
+            a.npos = lds.npos_word; a.off_node = lds.off_node;
             a.band_w = g->band_w;
             a.zu = zu; a.zd = zd; a.phi = phi; a.gam = gam; a.gu = gu; a.gd = gd;
             // staggered start (k_admm_lds): only when the launch runs several rounds of workgroups per CU
@@ -1970,7 +1997,7 @@ struct Engine : EngineBase {
                 MG_HIP(hipMemcpyAsync(x_out, xc, (size_t)B * TN * sizeof(float), hipMemcpyDeviceToDevice, st));
             if (state_out) {      // the state the caller asked for, in the reference's layout
                 auto out = [&](void* dst, const float* src) {
-                    return dst == nullptr ? (int)MGADMM_OK : mg_lds_state_layout(false, T, N, lds.TPG, B, src, (float*)dst, st);
+                    return dst == nullptr ? (int)MGADMM_OK : mg_lds_state_layout(false, T, N, lds.TPG, B, src, (float*)dst, lds_row_of_node(), st);
                 };
                 MG_TRY(out(state_out->zu, zu));
                 MG_TRY(out(state_out->zd, zd));

@@ -67,6 +67,11 @@ struct LdsArgs : LdsArgsCore {
     // other kernels read): workgroup b takes rho .. cx2 from sp[b] instead of the scalars above.  In these kernels the
     // per-sample stop test runs when pstop != nullptr
     const LdsSampleParams* sp;   // [B] device table
+    // Row plan of the uniform-row instances with a compile-time tail (lds_rows.h; read by those instances only; behind everything
+    // else: no offset that existing code reads moves)
+    unsigned long long npos;     // 4-bit field w: positions of the W_d^T table (leading entries + tail) wave w gathers -- the largest
+                                 // in-degree among its rows; the table width when the rows are in node order
+    int off_node;                // offset in the global image of node_of_row[NR]: the node in HBM of LDS row r (ghost rows: 0)
 };
 
 // Execution plan of k_admm_lds chosen by Engine::plan_lds
@@ -89,10 +94,13 @@ int mg_lds_iteration_ps(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t
 // the same with per-sample weights (a.sp != nullptr; mg_lds_iteration forwards to it), with or without the stop test
 int mg_lds_iteration_pp(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t st);
 // initial state (ADMM.py:528-544): x in the reference's sample-major layout, zu / zd / gamma* thread-major for time groups of TPG steps
+// (in row order: row_of_node as in mg_lds_state_layout)
 int mg_lds_init(bool masked, int T, int t_in, int N, int TPG, int B, float tm, float den, const float* y, const float* mask, float* x,
-                float* zu, float* zd, float* gam, float* gu, float* gd, int* nonfinite, hipStream_t st);
+                float* zu, float* zd, float* gam, float* gu, float* gd, int* nonfinite, const int* row_of_node, hipStream_t st);
 // one state vector (B, T, N) <-> thread-major layout of the LDS path (lds_kernels.h, lds_state_index); src != dst
-int mg_lds_state_layout(bool to_thread_major, int T, int N, int TPG, int B, const float* src, float* dst, hipStream_t st);
+// row_of_node (device, [N]; nullptr = identity): the thread-major vectors are in ROW order (the thread of row r owns node
+// node_of_row[r]), what a caller imports / exports stays in node order
+int mg_lds_state_layout(bool to_thread_major, int T, int N, int TPG, int B, const float* src, float* dst, const int* row_of_node, hipStream_t st);
 // delta_x_per_step on the sample-major layout (ADMM.py:614): scratch = double[TN * (1 + ceil(B/64))], out = double[T];
 // stop: device stop word (the kernels return at once when it is set) or nullptr
 int mg_lds_dxps(int T, int N, int B, const float* x, const float* xo, double* scratch, double* out, const int* stop, hipStream_t st);

@@ -309,6 +309,7 @@ struct LdsCtx {
     f2 wdiag;                                // diagonal weights {W_d[i][i] (uniform instances: the table rows hold the others), W_d^T[i][i]}
     int skip, q1;
     const float* band_w;
+    int npos;                                // ROWPLAN: positions of the W_d^T table this wave gathers (wave-uniform, a scalar register)
 
     __device__ __forceinline__ unsigned glb0() const { return 4u * (unsigned)(t0 * N + ig); }   // HBM byte offset of element k = 0 (element k: + 4 k N, added to the uniform base)
     __device__ __forceinline__ int own() const { return i * TS + t0; }            // LDS index of element k = 0
@@ -319,6 +320,10 @@ struct LdsCtx {
     // to another image adds the distance of the two images.
     static constexpr bool UNI = NU > 0 && ND > 0;
     static constexpr int NDO = ND > 0 ? ND - 1 : 0;          // entries of a uniform W_d row besides the diagonal one
+    // ROW PLAN (lds_rows.h; uniform-row instances with a compile-time tail): LDS row i is node ig = node_of_row[i] -- the rows
+    // with long W_d^T rows first -- and the wave gathers only the first `npos` positions of the W_d^T table (the largest
+    // in-degree among its rows; every later position of every lane is a {own row, 0} pad)
+    static constexpr bool ROWPLAN = UNI && TP >= 0;
     struct Rows {
         i2v u[NU > 0 ? NU : 1];
         i2v d[NDO > 0 ? NDO : 1];
@@ -384,20 +389,34 @@ struct LdsCtx {
     // that ends earlier holds {own row, weight 0} there -- consecutive lanes read consecutive rows, which cannot collide.
     // Same instruction slots as the per-lane loop it replaces (every wave of cfg2 holds a 9- or 10-entry row), but no
     // exec-mask bookkeeping, and with the pair count a compile-time constant (uniform instances) every pair is requested first.
+    // the first NP pairs of the thread's tail row: every pair requested first, then accumulated in order
+    template <int NP>
+    __device__ __forceinline__ void tail_pairs_n(const lds_i4* row, const float* base, float (&acc)[TPG]) const {
+        lds_i4 e2[NP > 0 ? NP : 1];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) e2[j] = row[j];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            float va[TPG], vb[TPG];
+            lds_load<TPG>(base + e2[j].x, va);
+            lds_load<TPG>(base + e2[j].z, vb);
+            wacc<TPG>(e2[j].xy, va, acc);
+            wacc<TPG>(e2[j].zw, vb, acc);
+        }
+    }
     __device__ __forceinline__ void gather_tail(const float* SRC, float (&acc)[TPG]) const {
         const float* base = SRC + t0;
         if constexpr (TP >= 0) {
             const lds_i4* row = reinterpret_cast<const lds_i4*>(tail_t + (size_t)i * 2 * TP);
-            lds_i4 e2[TP > 0 ? TP : 1];
-#pragma unroll
-            for (int j = 0; j < TP; ++j) e2[j] = row[j];
-#pragma unroll
-            for (int j = 0; j < TP; ++j) {
-                float va[TPG], vb[TPG];
-                lds_load<TPG>(base + e2[j].x, va);
-                lds_load<TPG>(base + e2[j].z, vb);
-                wacc<TPG>(e2[j].xy, va, acc);
-                wacc<TPG>(e2[j].zw, vb, acc);
+            if constexpr (ROWPLAN && TP > 0) {
+                // pair j only when the wave holds a row with more than LDS_NLEAD + 2 j entries: a branch on a scalar register
+                // (no exec mask), one fully batched variant per pair count.  A skipped pair would have added 0 * v: acc is
+                // bitwise what the full-width gather leaves
+                if constexpr (TP >= 3) if (npos > LDS_NLEAD + 4) { tail_pairs_n<3>(row, base, acc); return; }
+                if constexpr (TP >= 2) if (npos > LDS_NLEAD + 2) { tail_pairs_n<2>(row, base, acc); return; }
+                if (npos > LDS_NLEAD) tail_pairs_n<1>(row, base, acc);
+            } else {
+                tail_pairs_n<TP>(row, base, acc);
             }
         } else {
             const lds_i4* row = reinterpret_cast<const lds_i4*>(tail_t + (size_t)i * 2 * tail_pairs);
@@ -902,12 +921,25 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
     LdsCtx<TPG, BAND, NU, ND, TP> c;
     c.T = a.T; c.TS = a.TS; c.N = a.N;
     c.active = tid < a.nthreads;
+    constexpr bool ROWPLAN = LdsCtx<TPG, BAND, NU, ND, TP>::ROWPLAN;
+    // this wave's field of the row plan (LdsArgs::npos), kept in a scalar register
+    auto wave_npos = [&]() {
+        int n = 0;
+        if constexpr (ROWPLAN) {
+            n = (int)((a.npos >> (4 * __builtin_amdgcn_readfirstlane(tid >> 6))) & 15);
+            MG_PIN_S(n);
+        }
+        return n;
+    };
     {
         const int g = c.active ? tid / a.N : 0;
-        c.ig = c.active ? tid - g * a.N : 0;
-        c.i = c.active ? c.ig : a.N + (tid - a.nthreads);
+        const int r = c.active ? tid - g * a.N : 0;
+        c.i = c.active ? r : a.N + (tid - a.nthreads);
+        if constexpr (ROWPLAN) c.ig = a.csr[a.off_node + c.i];       // node_of_row (ghost rows: 0)
+        else c.ig = r;
         c.t0 = g * TPG;
     }
+    c.npos = wave_npos();
     c.P = P; c.Q = Q;
     c.skip = a.skip; c.q1 = a.q1; c.band_w = a.band_w;
     c.tail_pairs = a.tail_pairs;
@@ -1085,6 +1117,7 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
         c.active = tid < a.nthreads;
         c.so0 = c.active ? 4u * TPG * (unsigned)tid : 0u;
         br.lane = tid & 63; br.wave = tid >> 6;
+        c.npos = wave_npos();
     };
 
     // ---- first iteration only: phi = Ldr x0 (ADMM.py:541); the dual variables were filled by k_init_lds
@@ -1426,7 +1459,8 @@ template <bool MASKED>
 __global__ __launch_bounds__(256) void k_init_lds(int T, int t_in, int N, int TPG, int B, float tm, float den, const float* __restrict__ y,
                                                   const float* __restrict__ mask, float* __restrict__ x, float* __restrict__ zu,
                                                   float* __restrict__ zd, float* __restrict__ gam, float* __restrict__ gu,
-                                                  float* __restrict__ gd, int* __restrict__ nonfinite) {
+                                                  float* __restrict__ gd, int* __restrict__ nonfinite,
+                                                  const int* __restrict__ row_of_node) {
 #pragma clang fp contract(off)
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int b = blockIdx.y;
@@ -1465,9 +1499,11 @@ __global__ __launch_bounds__(256) void k_init_lds(int T, int t_in, int N, int TP
         return (w * (float)t + c0) * (1.f - mb[t * N + i]) + yb[t * N + i];
     };
     // a thread writes the TPG elements of one (time group, node) of the thread-major vectors as one contiguous run (consecutive
-    // nodes: consecutive runs), x in the reference's layout element by element (consecutive nodes: consecutive addresses)
+    // nodes: consecutive runs -- at the node's ROW when k_admm_lds owns its rows in another order), x in the reference's layout
+    // element by element (consecutive nodes: consecutive addresses)
+    const int ir = row_of_node ? row_of_node[i] : i;
     for (int t0 = 0; t0 < T; t0 += TPG) {
-        const size_t es = sb + (size_t)((t0 / TPG) * N + i) * TPG;
+        const size_t es = sb + (size_t)((t0 / TPG) * N + ir) * TPG;
         if (TPG % 4 == 0) {
             for (int k = 0; k < TPG; k += 4) {
                 lds_f4 q;
@@ -1494,12 +1530,13 @@ __global__ __launch_bounds__(256) void k_init_lds(int T, int t_in, int N, int TP
 
 // a state vector between the reference's (B, T, N) layout and the thread-major layout (warm start in, exported state out)
 template <bool TO_THREAD_MAJOR>
-__global__ __launch_bounds__(256) void k_state_layout(int T, int N, int TPG, const float* __restrict__ src, float* __restrict__ dst) {
+__global__ __launch_bounds__(256) void k_state_layout(int T, int N, int TPG, const float* __restrict__ src, float* __restrict__ dst,
+                                                      const int* __restrict__ row_of_node) {
     const int e = blockIdx.x * 256 + threadIdx.x;        // index in the reference layout
     if (e >= T * N) return;
     const size_t sb = (size_t)blockIdx.y * T * N;
     const int t = e / N, i = e - t * N;
-    const int es = lds_state_index(t, i, N, TPG);
+    const int es = lds_state_index(t, row_of_node ? row_of_node[i] : i, N, TPG);       // thread-major vectors are in row order
     if (TO_THREAD_MAJOR) dst[sb + es] = src[sb + e];
     else dst[sb + e] = src[sb + es];
 }
