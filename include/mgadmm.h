@@ -219,6 +219,9 @@ typedef enum {
     MGADMM_Q_LDS_CHUNK = 13,    /* ADMM iterations per k_admm_lds launch when the iteration count is fixed          */
     MGADMM_Q_LDS_ROWS = 14,     /* LDS rows of an image: nodes + ghost rows                                         */
     MGADMM_Q_CLDR_SLOTS = 15,   /* W_d^T entry slots per row of the fused Ldr^T Ldr kernel in use (12 / 16 / 24); 0: two-pass */
+    MGADMM_Q_LDS_CG_BARRIERS = 17,/* workgroup barriers per CG iteration of a cLdr solve (x, zd) in the planned k_admm_lds
+                                   instance: 4 (5 in single-buffer mode), or 3 in the uniform-row instances, which form p.Ap
+                                   from q.q ahead of the q exchange; 0 without the LDS path                              */
     MGADMM_Q_LDS_INSTANCE = 16  /* template arguments <TPG, BAND, MAXT, SB, NU, ND, SLOTS, TP> of the k_admm_lds instance the
                                    last LDS launch ran, packed: bits 0-7 TPG, 8 BAND, 9 SB, 10 SLOTS, 11-15 NU, 16-20 ND,
                                    21-31 MAXT, 32-39 TP + 1; -1 before the first launch                                   */

@@ -633,6 +633,7 @@ struct Engine : EngineBase {
             case MGADMM_Q_LDS_ROWS: *out = lds.NR; break;
             case MGADMM_Q_CLDR_SLOTS: *out = cldr_dev.state == 1 ? cl_gt : 0; break;      // (prepared by the first operator application)
             case MGADMM_Q_LDS_INSTANCE: *out = lds_instance; break;
+            case MGADMM_Q_LDS_CG_BARRIERS: *out = !lds.ok ? 0 : (lds.uniform45 ? 3 : 4 + lds.sb); break;      // lds_kernels.h: lds_fold_v
             case MGADMM_Q_NNZ_U: *out = g->hWu.nnz(); break;
             case MGADMM_Q_NNZ_D: *out = g->hWd.nnz(); break;
             case MGADMM_Q_NNZ_DT: *out = g->hWdT.nnz(); break;
@@ -1482,7 +1483,8 @@ struct Engine : EngineBase {
         int best = 0;
         const char* force = getenv("MGADMM_LDS_TPG");      // tests / experiments: force one time-group width
         // does the graph qualify for the uniform-row instances (TPG 8 and 12: table rows in registers, branch-free solves)?
-        bool uni_graph = g->mode != MGADMM_TEMPORAL_BAND && !getenv("MGADMM_LDS_SB") && !getenv("MGADMM_LDS_RAGGED");
+        // (not with transpose_by_gather: the uniform instances take p . A p from |Ldr p|^2, which needs the exact transpose of W_d)
+        bool uni_graph = g->mode != MGADMM_TEMPORAL_BAND && !g->transpose_by_gather && !getenv("MGADMM_LDS_SB") && !getenv("MGADMM_LDS_RAGGED");
         for (int i = 0; i < N && uni_graph; ++i) {
             int ndiag = 0;
             for (int e = g->hWd.rowptr[i]; e < g->hWd.rowptr[i + 1]; ++e) ndiag += g->hWd.col[e] == i;
@@ -1516,7 +1518,7 @@ struct Engine : EngineBase {
         lds.NR = NR;
         // kNN tables with k = 4 and no pads (the reference's setting): every W_u row has 4, every W_d row 5 entries -> the
         // instance with unrolled gathers that reads its rows from the global image
-        lds.uniform45 = (!band && (best == 8 || best == 12) && !lds.sb && !getenv("MGADMM_LDS_RAGGED")) ? 1 : 0;
+        lds.uniform45 = (!band && !g->transpose_by_gather && (best == 8 || best == 12) && !lds.sb && !getenv("MGADMM_LDS_RAGGED")) ? 1 : 0;
         for (int i = 0; i < N && lds.uniform45; ++i) {
             int ndiag = 0;
             for (int e = g->hWd.rowptr[i]; e < g->hWd.rowptr[i + 1]; ++e) ndiag += g->hWd.col[e] == i;

@@ -66,10 +66,31 @@ struct BlockRed {
     // 16 wave totals (slot lane & 15) and the 16 values are summed inside each 16-lane row with DPP row shifts
     // (all four rows compute the same sum in the same order); lane 15's value is broadcast.  8 VALU + 1 ds_read
     // instead of 15 VALU + 4 ds_read_b128 + two float<->double conversions per reduction.
-    __device__ __forceinline__ float sumf(float v) {
+    // In two halves, for a caller that has a barrier of its own between them (lds_apply, FOLD): publish() parks the wave
+    // total in the current half of `red`, total() -- after a barrier -- reads the 16 totals and moves on to the other half.
+    __device__ __forceinline__ void publish(float v) {
         v = wave_sum(v);
         float* buf = red + par * 16;
         if (lane == 0) buf[wave] = v;      // (all 64 lanes storing the same word instead: +1.2 % per launch)
+    }
+    __device__ __forceinline__ float total() { return total_of(total_read()); }
+    // ... and total() itself in two: the read of this lane's slot, and the sum of the 16 slots (a caller with LDS reads of its
+    // own after the barrier requests the slot first and sums when they are back: LDS answers in order)
+    __device__ __forceinline__ float total_read() const { return red[par * 16 + (lane & 15)]; }
+    __device__ __forceinline__ float total_of(float t) {
+        t = dpp_step<0x111, 0xf>(t);   // row_shr:1
+        t = dpp_step<0x112, 0xf>(t);   // row_shr:2
+        t = dpp_step<0x114, 0xf>(t);   // row_shr:4
+        t = dpp_step<0x118, 0xf>(t);   // row_shr:8   -> lane 15 of every row: sum of the 16 slots
+        par ^= 1;
+        return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 15));
+    }
+    // (sumf keeps its own text instead of calling publish / total: composed of them it compiles to other register allocations
+    // in a dozen generic instances, whose spill counts are pinned -- profiles/r07/kernel_registers.txt)
+    __device__ __forceinline__ float sumf(float v) {
+        v = wave_sum(v);
+        float* buf = red + par * 16;
+        if (lane == 0) buf[wave] = v;
         __syncthreads();
         float t = buf[lane & 15];
         t = dpp_step<0x111, 0xf>(t);   // row_shr:1
@@ -618,12 +639,26 @@ __device__ __forceinline__ void slot_get(const float* S, int tid, int nthr, floa
 // dc = diagonal coefficient of the own elements (H^T H or mask value, plus the rho/2 terms), see lds_diag.
 // Returns sum_k v_k * (A v)_k of the own elements.  Uses ctx.Q as scratch; contains a barrier for KIND 1.
 // Callers separate successive calls by barriers.  R: the thread's table rows in registers (uniform instances).
+//
+// FOLD (the cLdr operator of the uniform-row instances): returns v . A v of the WHOLE SAMPLE instead, without a barrier of its
+// own.  A = diag(dc) + c2 Ldr^T Ldr and the second gather uses the exact transpose of W_d (plan_lds gives a graph with
+// transpose_by_gather no uniform instance), so v . A v = sum dc_k v_k^2 + c2 sum q_k^2 with q = Ldr v: every q_k has one
+// owner (ghosts and time T hold zeros), and the thread knows its share BEFORE it stores q.  The wave total goes to `red` next
+// to the q store, the barrier that publishes q publishes it too, and the 16 totals are read under the W_d^T gather.  The
+// halves of br.red: this total is written before the barrier inside and read after it, r . r (lds_cg) is written and read
+// around the barrier after the application in the other half, the next application writes after that barrier and the one
+// in front of it.  Every call publishes and reads (also the init trip of lds_cg, which does not use the value): br.par
+// alternates as it does with two sumf per iteration.
+template <int KIND, bool BAND, bool SB, bool UNI>
+constexpr bool lds_fold_v = KIND == 1 && UNI && !BAND && !SB;
 template <int TPG, bool BAND, int KIND, bool SB, int NU, int ND, int TP>
-__device__ __forceinline__ float lds_apply(LdsCtx<TPG, BAND, NU, ND, TP>& c, const float (&v)[TPG], float (&av)[TPG], const float (&dc)[TPG],
-                                           float c2, typename LdsCtx<TPG, BAND, NU, ND, TP>::Rows& R) {
+__device__ __forceinline__ float lds_apply(LdsCtx<TPG, BAND, NU, ND, TP>& c, BlockRed& br, const float (&v)[TPG], float (&av)[TPG],
+                                           const float (&dc)[TPG], float c2, typename LdsCtx<TPG, BAND, NU, ND, TP>::Rows& R) {
     // the register entries, made opaque IN PLACE once per application: their weights must be splatted INSIDE the CG loop, where
     // the instruction selector folds the splat into the packed multiply-add (hoisted, it becomes a register pair per weight)
     typedef LdsCtx<TPG, BAND, NU, ND, TP> Ctx;
+    constexpr bool FOLD = lds_fold_v<KIND, BAND, SB, Ctx::UNI>;
+    float vAv = 0.f;         // FOLD: v . A v of the sample
     if constexpr (Ctx::UNI) {
         if (KIND == 1) {
 #pragma unroll
@@ -672,7 +707,20 @@ __device__ __forceinline__ float lds_apply(LdsCtx<TPG, BAND, NU, ND, TP>& c, con
             }
             if (SB) __syncthreads();           // single LDS vector (Q aliases P): every gather of p is done before q replaces it
             lds_store<TPG>(c.Q + c.own(), q);
+            if constexpr (FOLD) {
+                // sum dc_k v_k^2 as dc . (v * v): written dc * v * v, the optimiser shares dc * v with the product formed below and
+                // keeps those TPG values alive across the barrier and the gather (7 more spilled registers around the zd solve)
+                float vv[TPG];
+#pragma unroll
+                for (int j = 0; j < TPG / 2; ++j) {
+                    const f2 t = mk2(v[2 * j], v[2 * j + 1]) * mk2(v[2 * j], v[2 * j + 1]);
+                    vv[2 * j] = t.x; vv[2 * j + 1] = t.y;
+                }
+                br.publish(__builtin_fmaf(c2, dot<TPG>(q, q), dot<TPG>(dc, vv)));
+            }
             __syncthreads();
+            float slot = 0.f;
+            if constexpr (FOLD) slot = br.total_read();        // (requested ahead of the gather: LDS answers in order)
             {
                 float acc[TPG];
                 c.mul_wdt(c.Q, acc, R, q);          // diagonal term: position t0+k of the thread's own q row = q[k] (registers)
@@ -683,6 +731,10 @@ __device__ __forceinline__ float lds_apply(LdsCtx<TPG, BAND, NU, ND, TP>& c, con
                 l[0] = (has_prev ? qprev : 0.f) - acc[0];
 #pragma unroll
                 for (int k = 1; k < TPG; ++k) l[k] = q[k - 1] - acc[k];
+            }
+            if constexpr (FOLD) {
+                MG_PIN_V(slot);           // (the sum of the slots after the gather, not in front of it with a wait of its own)
+                vAv = br.total_of(slot);
             }
         }
     } else if (KIND == 2) {
@@ -700,7 +752,8 @@ __device__ __forceinline__ float lds_apply(LdsCtx<TPG, BAND, NU, ND, TP>& c, con
 #pragma unroll
         for (int k = 0; k < TPG; ++k) av[k] = (KIND == 0) ? dc[k] * v[k] : __builtin_fmaf(c2, l[k], dc[k] * v[k]);
     }
-    return dot<TPG>(v, av);
+    if constexpr (FOLD) return vAv;
+    else return dot<TPG>(v, av);
 }
 // diagonal coefficient d + c1 of the own elements: d = dg[el] when dg != nullptr (mask values, global
 // memory), else [hth && t < t_in]   (ADMM.py:371-379: H^T H x resp. mask * x; ADMM.py:381-399: none)
@@ -747,7 +800,7 @@ __device__ __forceinline__ int lds_cg(LdsCtx<TPG, BAND, NU, ND, TP>& c, BlockRed
     bool done = false, init = true;
     for (int it = -1; it < max_cg && !done; ++it) {
         __syncthreads();                 // p complete in LDS
-        const float part = lds_apply<TPG, BAND, KIND, SB, NU, ND, TP>(c, pv, av, dc, c2, R);
+        const float part = lds_apply<TPG, BAND, KIND, SB, NU, ND, TP>(c, br, pv, av, dc, c2, R);
         if (init) {                      // workgroup-uniform
             init = false;
             if (dmask != nullptr) lds_diag<TPG, BAND, NU, ND, TP>(c, nullptr, hth, t_in, c1, dc);     // quirk Q2: iterations use [t < t_in]
@@ -760,7 +813,11 @@ __device__ __forceinline__ int lds_cg(LdsCtx<TPG, BAND, NU, ND, TP>& c, BlockRed
             c.template put<0>(c.P, pv);
             continue;
         }
-        const float pAp = br.sumf(part);         // barrier: every gather from P/Q of this iteration is done
+        // FOLD: lds_apply has summed p . A p over the sample already -- no barrier here; the one of r . r below is the next, and
+        // no thread reaches it before its gathers from P / Q are done (its r needs them)
+        float pAp;
+        if constexpr (lds_fold_v<KIND, BAND, SB, LdsCtx<TPG, BAND, NU, ND, TP>::UNI>) pAp = part;
+        else pAp = br.sumf(part);                // barrier: every gather from P/Q of this iteration is done
         // alpha, beta through v_rcp_f32 (1 ulp) instead of the correctly rounded division (a chain of ~10 dependent
         // instructions every thread waits for, twice per iteration: -2.9 % per launch).  The coefficients differ from
         // the IEEE quotient by at most 1.5 ulp -- below the rounding noise of the dot products they are formed from;
