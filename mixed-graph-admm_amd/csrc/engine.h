@@ -14,8 +14,7 @@
 #include "cldr_tiles.h"
 #include "stream_kernels.h"
 #include "lds_args.h"
-#include "lds_banks.h"
-#include "lds_rows.h"
+#include "lds_plan.h"
 
 namespace {
 
@@ -35,8 +34,8 @@ constexpr int NRED_MAX = 6;
 constexpr int PROF_POOL = 32768;
 constexpr int LDS_SETS = 3;             // interior iterate-buffer sets / per-sample metric sets of the chunked schedule (chunks in flight)
 constexpr int LDS_NBOUND = 4;           // iterate buffers at the chunk boundaries
-constexpr int LDS_MAXJ_POOL = LDS_MAXJ;   // longest chunk of the LDS path's chunked schedule: 2 (J - 1) + 3 iterate buffers -- 15 out of the
-                                          // workspace (enough for J = 7), the rest allocated on the first solve that asks for a longer chunk
+constexpr int LDS_MAXJ_POOL = LDS_MAXJ;   // longest chunk of the LDS path's chunked schedule: LDS_SETS (J - 1) + LDS_NBOUND iterate buffers -- 15
+                                          // out of the workspace (enough for J = 4), the rest allocated on the first solve that asks for a longer chunk
 constexpr int NACT_LOG = 1 << 16;   // pinned log of the per-iteration active-sample counts (one int per CG iteration enqueued)
 
 template <typename S>
@@ -85,16 +84,8 @@ struct Engine : EngineBase {
     int use_tile = 1;             // LDS-tiled spatial kernel on cluster-ordered graphs (reorder = 2); MGADMM_TILE=0 disables
     int64_t ws_bytes = 0;
     // LDS-resident fused path (float32, small graphs)
-    struct LdsPlan {
-        bool ok = false;
-        int G = 0, TPG = 0, TS = 0, nthreads = 0, block = 0, NR = 0, csr_ints = 0, maxt = 1024, sb = 0, uniform45 = 0, slots = 0;
-        int tail_pairs = 0, lds_img0 = 0, lds_img_ints = 0;
-        int off_rp_u = 0, off_rp_d = 0, off_en_u = 0, off_en_d = 0, off_lead_t = 0, off_tail_t = 0, off_diag = 0;
-        int row_order = 0;            // ldsrows::Order of the thread -> row map (lds_rows.h); 0: node order
-        int off_node = 0, off_rown = 0;   // node_of_row [NR] / row_of_node [N] in the global image
-        uint64_t npos_word = 0;       // table positions per wave, 4-bit fields (LdsArgs::npos)
-        size_t lds_bytes = 0;
-    } lds;
+    using LdsPlan = ldsplan::LdsPlan;
+    LdsPlan lds;
     int* d_lds_csr = nullptr;
     double* d_m2 = nullptr;
     // ADMM outer loop of the LDS path without host round trips (solve_lds): device stop word, second metric buffer, helper
@@ -111,7 +102,7 @@ struct Engine : EngineBase {
     int sp_B = 0;                 // samples of the table; 0 = none set
     std::vector<double> sp_val[6];   // rho, rho_u, rho_d, mu_u, mu_d1, mu_d2
     LdsSampleParams* d_sp = nullptr;   // [Bmax]
-    std::vector<float*> lds_ring_extra;   // iterate buffers beyond the 15 workspace vectors (chunks longer than 7 iterations)
+    std::vector<float*> lds_ring_extra;   // iterate buffers beyond the 15 workspace vectors (chunks longer than 4 iterations)
     int64_t lds_instance = -1;       // MGADMM_Q_LDS_INSTANCE: template arguments of the k_admm_lds instance of the last launch
     int lds_chunk = LDS_MAXJ_POOL;   // MGADMM_LDS_CHUNK: ADMM iterations per k_admm_lds launch when the iteration count is fixed (1 .. LDS_MAXJ_POOL)
     hipStream_t st_side = nullptr;
@@ -633,7 +624,7 @@ struct Engine : EngineBase {
             case MGADMM_Q_LDS_ROWS: *out = lds.NR; break;
             case MGADMM_Q_CLDR_SLOTS: *out = cldr_dev.state == 1 ? cl_gt : 0; break;      // (prepared by the first operator application)
             case MGADMM_Q_LDS_INSTANCE: *out = lds_instance; break;
-            case MGADMM_Q_LDS_CG_BARRIERS: *out = !lds.ok ? 0 : (lds.uniform45 ? 3 : 4 + lds.sb); break;      // lds_kernels.h: lds_fold_v
+            case MGADMM_Q_LDS_CG_BARRIERS: *out = lds.ok ? lds.cg_barriers : 0; break;
             case MGADMM_Q_NNZ_U: *out = g->hWu.nnz(); break;
             case MGADMM_Q_NNZ_D: *out = g->hWd.nnz(); break;
             case MGADMM_Q_NNZ_DT: *out = g->hWdT.nnz(); break;
@@ -1479,218 +1470,17 @@ struct Engine : EngineBase {
         lds = LdsPlan();
         if (hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess) { (void)hipGetLastError(); dev_cus = 0; }
         if (!std::is_same<S, float>::value) return MGADMM_OK;
-        const int tpgs[] = {1, 2, 3, 4, 6, 8, 12};
-        int best = 0;
-        const char* force = getenv("MGADMM_LDS_TPG");      // tests / experiments: force one time-group width
-        // does the graph qualify for the uniform-row instances (TPG 8 and 12: table rows in registers, branch-free solves)?
-        // (not with transpose_by_gather: the uniform instances take p . A p from |Ldr p|^2, which needs the exact transpose of W_d)
-        bool uni_graph = g->mode != MGADMM_TEMPORAL_BAND && !g->transpose_by_gather && !getenv("MGADMM_LDS_SB") && !getenv("MGADMM_LDS_RAGGED");
-        for (int i = 0; i < N && uni_graph; ++i) {
-            int ndiag = 0;
-            for (int e = g->hWd.rowptr[i]; e < g->hWd.rowptr[i + 1]; ++e) ndiag += g->hWd.col[e] == i;
-            uni_graph = g->hWu.rowptr[i + 1] - g->hWu.rowptr[i] == 4 && g->hWd.rowptr[i + 1] - g->hWd.rowptr[i] == 5 && ndiag == 1;
-        }
-        for (int tpg : tpgs) {
-            if (T % tpg) continue;
-            const int G = T / tpg;
-            if ((long)N * G > 1024) continue;
-            if (force && atoi(force) != tpg) continue;
-            if (!best) best = tpg;        // smallest TPG = most threads ...
-            if (uni_graph && !force && tpg == 8) best = 8;      // ... unless the uniform-row instance of width 8 applies: it is the
-                                                                 // fastest form also for graphs small enough for narrower groups
-        }
-        if (!best) return MGADMM_OK;
-        const bool band = g->mode == MGADMM_TEMPORAL_BAND;
-        // (Twelve time steps per thread in a 640-thread workgroup -- 10 waves, 168 registers per thread, MGADMM_LDS_TPG=12 -- were
-        // 5 % ahead of eight in a 960-thread one while the eight-step instance still spilled around its solves, and are 4 %
-        // behind since it does not: cfg2 2.08 M against 2.17 M sample-iterations/s.  The smallest width stays the default.)
-        const int sb_env = getenv("MGADMM_LDS_SB") ? atoi(getenv("MGADMM_LDS_SB")) : 0;   // 1: one LDS vector for p and q (experiments)
-        lds.TPG = best;
-        lds.G = T / best;
-        lds.nthreads = N * lds.G;
-        lds.block = (lds.nthreads + 63) / 64 * 64;
-        // register budget: the kernel is compiled for the smallest workgroup-size class that holds the block
-        lds.maxt = (best == 12 && lds.block <= 640) ? 640 : 1024;
-        lds.sb = (sb_env && ((best == 12 && lds.maxt == 640) || best == 8)) ? 1 : 0;
-        // the threads of the last wave that own no element are GHOSTS (lds_kernels.h): each gets an LDS row of zeros and table
-        // rows of zero weights
-        const int NR = N + (lds.block - lds.nthreads);
-        lds.NR = NR;
-        // kNN tables with k = 4 and no pads (the reference's setting): every W_u row has 4, every W_d row 5 entries -> the
-        // instance with unrolled gathers that reads its rows from the global image
-        lds.uniform45 = (!band && !g->transpose_by_gather && (best == 8 || best == 12) && !lds.sb && !getenv("MGADMM_LDS_RAGGED")) ? 1 : 0;
-        for (int i = 0; i < N && lds.uniform45; ++i) {
-            int ndiag = 0;
-            for (int e = g->hWd.rowptr[i]; e < g->hWd.rowptr[i + 1]; ++e) ndiag += g->hWd.col[e] == i;
-            if (g->hWu.rowptr[i + 1] - g->hWu.rowptr[i] != 4 || g->hWd.rowptr[i + 1] - g->hWd.rowptr[i] != 5 || ndiag != 1) lds.uniform45 = 0;
-        }
-        // diagonal entries: W_d^T[i][i] (every instance) and W_d[i][i] (uniform instances) are kept out of the tables -- inside a
-        // CG solve their operand is the thread's own vector (registers): no LDS read
-        std::vector<float> diag_d(NR, 0.f), diag_t(NR, 0.f);
-        auto strip_diag = [&](const HostCsr& h, std::vector<float>& dg) {
-            HostCsr o;
-            o.rowptr.push_back(0);
-            for (int i = 0; i < N; ++i) {
-                for (int e = h.rowptr[i]; e < h.rowptr[i + 1]; ++e) {
-                    if (h.col[e] == i) dg[i] += h.val[e];
-                    else { o.col.push_back(h.col[e]); o.val.push_back(h.val[e]); }
-                }
-                o.rowptr.push_back((int)o.col.size());
-            }
-            return o;
-        };
-        // W_d^T: LDS_NLEAD leading entries per row + a tail table of 2 * tail_pairs entries per row (rows padded with
-        // {own row, weight 0}): one table width for every lane of the workgroup
-        std::vector<int> deg_t(N, 0);                         // off-diagonal in-degree of W_d = length of a W_d^T row
-        if (!band)
-            for (int i = 0; i < N; ++i)
-                for (int e = g->hWdT.rowptr[i]; e < g->hWdT.rowptr[i + 1]; ++e) deg_t[i] += g->hWdT.col[e] != i;
-        const int maxlen_t = N > 0 ? *std::max_element(deg_t.begin(), deg_t.end()) : 0;
-        const int tp = band ? 0 : (std::max(0, maxlen_t - LDS_NLEAD) + 1) / 2;
-        const int WT = LDS_NLEAD + 2 * tp;
-        lds.tail_pairs = tp;
-        // ROW PLAN (lds_rows.h) of the uniform-row instances with a compile-time tail (tail_pairs <= 3, lds_dispatch.h): the rows
-        // that need tail pairs are owned by the first threads of every time group, so that most waves hold rows that fit the
-        // leading entries and gather no tail pair at all (a wave gathers as many table positions as its longest row holds).
-        // From here on this function works on the relabelled graph (row numbers); node numbers stay in the HBM-facing indices
-        // (node_of_row for k_admm_lds, row_of_node for k_init_lds / k_state_layout).
-        // MGADMM_LDS_ROW_ORDER: 2 (default) = by tail pairs needed, node order inside a class; 1 = by in-degree (fewest positions,
-        // but the neighbours of consecutive lanes are scattered: the bank conflicts of all three gathers cost more than the
-        // positions save); 0 = node order and full counts (the A/B leg).  The other instances: always node order.
-        const char* ro_env = getenv("MGADMM_LDS_ROW_ORDER");
-        lds.row_order = (lds.uniform45 && tp <= 3) ? (ro_env ? std::max(0, std::min(atoi(ro_env), 2)) : (int)ldsrows::TAIL_CLASS) : 0;
-        const ldsrows::Plan rows = ldsrows::make_plan(deg_t, lds.G, WT, lds.row_order, LDS_NLEAD);
-        lds.npos_word = 0;
-        if (lds.uniform45 && tp <= 3 && !ldsrows::pack_npos(rows, &lds.npos_word)) {
-            mg_set_error("lds: row plan does not fit its launch word (%d waves)", (int)rows.npos.size());
+        // which k_admm_lds instance, its geometry and the image of its tables: plain host code, lds_plan.h
+        std::vector<int> img;
+        const ldsplan::Input in{T, N, g->mode == MGADMM_TEMPORAL_BAND, g->transpose_by_gather != 0, g->hWu, g->hWd, g->hWdT};
+        const ldsplan::Status planned = ldsplan::make(in, ldsplan::Switches::from_env(), lds, img);
+        if (planned == ldsplan::ROWS_DO_NOT_FIT) {
+            mg_set_error("lds: row plan does not fit its launch word (%d waves)", lds.block / 64);
             return MGADMM_ERR_INVALID;
         }
-        const HostCsr Wu = lds.row_order ? ldsrows::relabel(g->hWu, rows) : g->hWu;
-        const HostCsr Wd = lds.row_order ? ldsrows::relabel(g->hWd, rows) : g->hWd;
-        const HostCsr WdT = lds.row_order ? ldsrows::relabel(g->hWdT, rows) : g->hWdT;
-        const HostCsr hWdT_off = band ? HostCsr() : strip_diag(WdT, diag_t);
-        const HostCsr hWd_tab = band ? HostCsr() : (lds.uniform45 ? strip_diag(Wd, diag_d) : Wd);
-        // host tables with the ghosts' rows appended
-        auto with_ghosts = [&](const HostCsr& h, int fixed_len) {
-            HostCsr o;
-            o.rowptr.assign(h.rowptr.begin(), h.rowptr.begin() + N + 1);
-            o.col = h.col; o.val = h.val;
-            for (int r = N; r < NR; ++r) {
-                for (int e = 0; e < fixed_len; ++e) { o.col.push_back(r); o.val.push_back(0.f); }
-                o.rowptr.push_back((int)o.col.size());
-            }
-            return o;
-        };
-        const HostCsr hu = with_ghosts(Wu, lds.uniform45 ? 4 : 0);
-        const HostCsr hd = band ? HostCsr() : with_ghosts(hWd_tab, lds.uniform45 ? 4 : 0);
-        const int nu = hu.nnz(), nd = band ? 0 : hd.nnz();
-        auto al4 = [](int v) { return (v + 3) & ~3; };
-        int off = 0;
-        lds.off_rp_u = off; off += NR + 1;
-        lds.off_rp_d = off; off += NR + 1;
-        off = al4(off);
-        lds.off_en_u = off; off += 2 * nu;
-        lds.off_en_d = off; off += 2 * nd;
-        lds.off_lead_t = off; off += 2 * NR * LDS_NLEAD;
-        off = al4(off);
-        lds.off_tail_t = off; off += 2 * NR * 2 * tp + 4;     // + one pair: gather_tail requests the next pair ahead
-        const int tail_ints = off - lds.off_tail_t;
-        lds.off_diag = off; off += 2 * NR;
-        off += 8;                                            // the paired loops of the ragged gathers read three entries ahead
-        lds.off_node = off; off += NR;                       // node_of_row (ghost rows: 0), read by k_admm_lds once per trip
-        lds.off_rown = off; off += N;                        // row_of_node, read by k_init_lds / k_state_layout
-        lds.csr_ints = off;
-        lds.lds_img0 = lds.uniform45 ? lds.off_tail_t : 0;
-        lds.lds_img_ints = lds.uniform45 ? tail_ints : lds.off_diag;
-        // LDS row stride: T padded to an odd number of 16-byte slots (rows then start on every bank group);
-        // fall back to the unpadded stride when the padded vectors do not fit
-        int ts = (T + 3) / 4 * 4;
-        if (((ts / 4) & 1) == 0) ts += 4;
-        auto bytes_for = [&](int stride, int slots) {
-            const size_t LN = (size_t)NR * stride;
-            return sizeof(float) * ((lds.sb ? 1 : 2) * LN + ((4 - (LN & 3)) & 3) + 32 + 16 * 12 + (size_t)slots * 2 * lds.block * best)
-                   + sizeof(int) * (size_t)lds.lds_img_ints;
-        };
-        if (bytes_for(ts, 0) > 160 * 1024) ts = T;
-        lds.TS = ts;
-        if (bytes_for(ts, 0) > 160 * 1024) { lds = LdsPlan(); return MGADMM_OK; }
-        // two more LDS vectors for per-thread operands (uniform instance): when they fit beside the padded images
-        lds.slots = (lds.uniform45 && !getenv("MGADMM_LDS_NOSLOTS") && bytes_for(ts, 1) <= 160 * 1024) ? 1 : 0;
-        lds.lds_bytes = bytes_for(ts, lds.slots);
-        std::vector<int> img(off, 0);
-        // Bank-aware entry order (lds_banks.h).  A gather instruction reads entry e of 64 consecutive threads' rows (64
-        // consecutive nodes, mostly); ds_read_b128 serves it in four groups of 16 lanes, and two lanes of a group collide
-        // when their neighbour rows start in the same 16-byte slot of the 256-byte bank line.  WHICH neighbour sits in entry
-        // e of a row is free.  Round 1 kept the table order (36 % of the LDS cycles of k_admm_lds were bank conflicts); round 2
-        // a greedy order, rows in node order, as the start of a min-conflicts search against an exact replay of the kernel's
-        // read stream (ldsbank::improve_targeted): cfg2 goes from 7 800 to 1 200 weighted conflict cycles in 0.15 s of host
-        // time per solver.  The sum of a row runs in the chosen order (fixed per graph: repeatable).
-        // MGADMM_LDS_TABLE_ORDER=1 keeps the table order, MGADMM_LDS_BANK_SEARCH=<steps> sets the search length (0: greedy only).
-        const bool bank_order = !band && best % 4 == 0 && ((lds.TS / 4) & 1) && !getenv("MGADMM_LDS_TABLE_ORDER");
-        long search_steps = 4000;
-        if (const char* e = getenv("MGADMM_LDS_BANK_SEARCH")) search_steps = atol(e);
-        // order[e] = index into h.col / h.val of the entry the kernel reads at position e (real rows only; ghosts' rows follow as they are)
-        auto slot_order = [&](const HostCsr& h, ldsbank::Stream stream) {
-            std::vector<int> order(h.nnz());
-            for (int e = 0; e < h.nnz(); ++e) order[e] = e;
-            if (!bank_order || h.nnz() == 0) return order;
-            ldsbank::Geometry q;
-            q.N = N; q.G = T / best; q.TPG = best; q.TS = lds.TS; q.nlead = LDS_NLEAD;
-            ldsbank::Mat m;
-            m.rowptr.assign(h.rowptr.begin(), h.rowptr.begin() + N + 1);
-            m.col.assign(h.col.begin(), h.col.begin() + h.rowptr[N]);
-            m.src.assign(order.begin(), order.begin() + h.rowptr[N]);
-            m.stream = stream;
-            ldsbank::greedy_order(q, m);
-            if (search_steps > 0) {
-                std::vector<int> pos(N);
-                for (int i = 0; i < N; ++i) pos[i] = i;
-                const ldsbank::Result r = ldsbank::improve_targeted(q, m, pos, search_steps);
-                if (getenv("MGADMM_LDS_BANK_STATS"))
-                    fprintf(stderr, "[mgadmm] lds bank search: stream %d, %d entries: %.0f -> %.0f conflict cycles per application (%ld steps)\n",
-                            (int)stream, h.rowptr[N], r.before, r.after, r.moves);
-            }
-            for (int e = 0; e < h.rowptr[N]; ++e) order[e] = m.src[e];
-            return order;
-        };
-        auto put_entry = [&](int at, int col, float w) {
-            img[at] = col * lds.TS;                           // LDS float offset of the neighbour's time row
-            memcpy(&img[at + 1], &w, 4);
-        };
-        auto put_csr = [&](const HostCsr& h, int off_rp, int off_en, ldsbank::Stream stream) {
-            const std::vector<int> order = slot_order(h, stream);
-            for (int i = 0; i <= NR; ++i) img[off_rp + i] = h.rowptr[i];
-            for (int e = 0; e < h.nnz(); ++e) put_entry(off_en + 2 * e, h.col[order[e]], h.val[order[e]]);
-        };
-        const ldsbank::Stream fixed_or_pairs = lds.uniform45 ? ldsbank::FIXED : ldsbank::PAIRS;     // gather_regs / gather
-        put_csr(hu, lds.off_rp_u, lds.off_en_u, fixed_or_pairs);
-        if (!band) {
-            put_csr(hd, lds.off_rp_d, lds.off_en_d, fixed_or_pairs);
-            // W_d^T as a table of WT entries per row: the row's entries, then {own row, 0}; every lane reads every position
-            // (FIXED stream of the bank model), the first LDS_NLEAD positions from registers, the others from the tail table
-            // With a row plan the entries of row r sit in the positions below lim[r] (what every wave that owns the row gathers).
-            ldsbank::Geometry q;
-            q.N = N; q.G = T / best; q.TPG = best; q.TS = lds.TS; q.nlead = LDS_NLEAD;
-            ldsbank::Result sr;
-            const ldsrows::Table ht = ldsrows::build_table(q, hWdT_off.rowptr, hWdT_off.col, hWdT_off.val, rows, WT, bank_order, search_steps, &sr);
-            if (bank_order && search_steps > 0 && getenv("MGADMM_LDS_BANK_STATS"))
-                fprintf(stderr, "[mgadmm] lds bank search: W_d^T table, %d entries: %.0f -> %.0f conflict cycles per application (%ld steps)\n",
-                        hWdT_off.rowptr[N], sr.before, sr.after, sr.moves);
-            for (int r = 0; r < NR; ++r)
-                for (int e = 0; e < WT; ++e) {
-                    const int at = e < LDS_NLEAD ? lds.off_lead_t + 2 * (r * LDS_NLEAD + e)
-                                                 : lds.off_tail_t + 2 * (r * 2 * tp + (e - LDS_NLEAD));
-                    if (r < N) put_entry(at, ht.col[(size_t)r * WT + e], ht.val[(size_t)r * WT + e]);
-                    else put_entry(at, r, 0.f);
-                }
-            put_entry(lds.off_tail_t + 2 * NR * 2 * tp, 0, 0.f);
-            put_entry(lds.off_tail_t + 2 * NR * 2 * tp + 2, 0, 0.f);
-            memcpy(&img[lds.off_diag], diag_d.data(), sizeof(float) * NR);
-            memcpy(&img[lds.off_diag + NR], diag_t.data(), sizeof(float) * NR);
-        }
-        for (int r = 0; r < N; ++r) { img[lds.off_node + r] = rows.node_of_row[r]; img[lds.off_rown + r] = rows.row_of_node[r]; }
-        MG_HIP(hipMalloc(&d_lds_csr, sizeof(int) * off));
-        MG_HIP(hipMemcpy(d_lds_csr, img.data(), sizeof(int) * off, hipMemcpyHostToDevice));
+        if (planned == ldsplan::NO_PLAN) return MGADMM_OK;
+        MG_HIP(hipMalloc(&d_lds_csr, sizeof(int) * img.size()));
+        MG_HIP(hipMemcpy(d_lds_csr, img.data(), sizeof(int) * img.size(), hipMemcpyHostToDevice));
         MG_HIP(hipMalloc(&d_m2, sizeof(double) * T * N * (1 + (size_t)(Bmax + 63) / 64)));
         MG_HIP(hipMalloc(&d_stop, sizeof(int)));
         MG_HIP(hipMemset(d_stop, 0, sizeof(int)));
@@ -1707,7 +1497,6 @@ struct Engine : EngineBase {
             for (auto& e : ev_main) MG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
             for (auto& e : ev_side) MG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
-        lds.ok = true;
         return MGADMM_OK;
     }
 
@@ -1716,7 +1505,7 @@ struct Engine : EngineBase {
 
     int launch_lds(const LdsArgs& a, int B) {
         const bool timed = prof_open(0, 0.0);
-        LdsLaunch L{lds.TPG, lds.maxt, lds.sb, lds.uniform45, lds.slots, lds.block, lds.lds_bytes, &lds_instance};
+        LdsLaunch L{lds.instance, lds.block, lds.lds_bytes, &lds_instance};
         const int rc = mg_lds_iteration(L, a, B, st);
         if (timed) prof_close();
         return rc;
@@ -1789,7 +1578,7 @@ struct Engine : EngineBase {
             static const int ring_ids[] = {V_XA, V_XB, V_ZUB, V_ZDB, V_PHIB, V_Y, V_MASK, V_R, V_P, V_Q, V_AP, V_RHS, V_TMP, V_IO0, V_IO1};
             constexpr int NRING = (int)(sizeof(ring_ids) / sizeof(ring_ids[0]));
             const int J = sched == CHUNKS ? std::max(1, std::min(std::min(lds_chunk, LDS_MAXJ_POOL), max_it)) : 1;
-            {   // buffers beyond the workspace vectors for chunks longer than 7 iterations (kept for the solver's lifetime)
+            {   // buffers beyond the workspace vectors for chunks longer than 4 iterations (kept for the solver's lifetime)
                 const int need = LDS_SETS * (J - 1) + LDS_NBOUND - NRING;
                 while ((int)lds_ring_extra.size() < need) {
                     float* b = nullptr;

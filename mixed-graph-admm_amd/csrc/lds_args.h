@@ -2,10 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-// entries of a W_d^T row that k_admm_lds keeps in registers during a CG solve (the rest of the row: the padded tail table)
-constexpr int LDS_NLEAD = 5;
-// most ADMM iterations one k_admm_lds launch runs (LdsArgs::J; the x pointer table has one entry more)
-constexpr int LDS_MAXJ = 16;
+#include "lds_consts.h"     // LDS_NLEAD, LDS_MAXJ, lds_instance_key
 
 // scalar part of the launch arguments: a trip of the loop inside k_admm_lds reads it from the kernarg segment
 struct LdsArgsCore {
@@ -74,14 +71,11 @@ struct LdsArgs : LdsArgsCore {
     int off_node;                // offset in the global image of node_of_row[NR]: the node in HBM of LDS row r (ghost rows: 0)
 };
 
-// Execution plan of k_admm_lds chosen by Engine::plan_lds
+// Execution plan of k_admm_lds chosen by ldsplan::make (lds_plan.h)
 struct LdsLaunch {
-    int tpg;        // time steps per thread
-    int maxt;       // workgroup-size class the kernel was compiled for (640 / 1024)
-    int sb;         // single LDS vector (two workgroups per CU with the 640-thread class)
-    int uniform45;  // every W_u row has 4 and every W_d row 5 entries (k = 4 table without pads): unrolled gathers, entries
-                    // read from the global image once per solve
-    int slots;      // uniform45 only: two more LDS vectors hold per-thread operands across the solves of an iteration
+    int64_t key;    // lds_instance_key of the instance: time steps per thread, band mode, workgroup-size class (640 / 1024),
+                    // single LDS vector, uniform rows (4 entries per W_u row, 5 per W_d row: unrolled gathers, entries read
+                    // from the global image once per solve), slot vectors for per-thread operands, compile-time tail pairs
     int block;      // threads per workgroup
     size_t lds_bytes;
     int64_t* instance;  // receives the packed template arguments of the instance launched (MGADMM_Q_LDS_INSTANCE), or nullptr

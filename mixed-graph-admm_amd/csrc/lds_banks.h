@@ -1,5 +1,5 @@
 // LDS bank model of the gathers of k_admm_lds (lds_kernels.h) and the host-side search that arranges the LDS image for
-// it.  Plain C++, no HIP: compiled into libmgadmm.so (Engine::plan_lds) and into the CPU check tests/cpu/lds_banks_check.cpp.
+// it.  Plain C++, no HIP: compiled into libmgadmm.so (ldsplan::make, lds_plan.h) and into the CPU check tests/cpu/lds_banks_check.cpp.
 //
 // A gather instruction of the kernel is one ds_read_b128 per lane: lane (g, i) -- node i, time group g -- reads 16 bytes of
 // the LDS row of the neighbour in entry e of ITS CSR row.  The hardware serves a wave's ds_read_b128 in four groups of 16

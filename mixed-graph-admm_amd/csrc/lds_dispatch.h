@@ -25,23 +25,32 @@ int allow_lds(const void* fn, int bytes) {
     return MGADMM_OK;
 }
 
-template <int TPG, bool BAND, int MAXT, bool SB, int NU = 0, int ND = 0, bool SLOTS = false, int TP = -1>
+// The instances the library ships, as the template arguments <TPG, BAND, MAXT, SB, NU, ND, SLOTS, TP> of k_admm_lds
+// (lds_kernels.h; tests/lds_census.py holds a problem for each).  Generic instances (ragged rows or band mode): every width
+// in the 1024-thread class, width 12 also in the 640-thread class; a single LDS vector (SB) for 12 / 640 and 8 / 1024.
+// Uniform-row instances (4 entries per W_u row, 5 per W_d row): widths 8 and 12, the pair count TP of the W_d^T tail table
+// a compile-time constant up to 3 pairs (-1: longer tails, pair count at run time), with and without slot vectors --
+// without only in the 1024-thread class of width 12 (342 .. 512 nodes in two time groups), which has no room for them.
+#define MG_LDS_GENERIC(X, TPG, MAXT, SB) X(TPG, false, MAXT, SB, 0, 0, false, -1) X(TPG, true, MAXT, SB, 0, 0, false, -1)
+#define MG_LDS_UNIFORM(X, TPG, MAXT, SLOTS) \
+    X(TPG, false, MAXT, false, 4, 5, SLOTS, 0) X(TPG, false, MAXT, false, 4, 5, SLOTS, 1) X(TPG, false, MAXT, false, 4, 5, SLOTS, 2) \
+    X(TPG, false, MAXT, false, 4, 5, SLOTS, 3) X(TPG, false, MAXT, false, 4, 5, SLOTS, -1)
+#define MG_LDS_INSTANCES(X) \
+    MG_LDS_GENERIC(X, 1, 1024, false) MG_LDS_GENERIC(X, 2, 1024, false) MG_LDS_GENERIC(X, 3, 1024, false) MG_LDS_GENERIC(X, 4, 1024, false) \
+    MG_LDS_GENERIC(X, 6, 1024, false) MG_LDS_GENERIC(X, 8, 1024, false) MG_LDS_GENERIC(X, 12, 1024, false) MG_LDS_GENERIC(X, 12, 640, false) \
+    MG_LDS_GENERIC(X, 12, 640, true) MG_LDS_GENERIC(X, 8, 1024, true) \
+    MG_LDS_UNIFORM(X, 8, 1024, false) MG_LDS_UNIFORM(X, 8, 1024, true) MG_LDS_UNIFORM(X, 12, 640, false) MG_LDS_UNIFORM(X, 12, 640, true) \
+    MG_LDS_UNIFORM(X, 12, 1024, false)
+
+template <int TPG, bool BAND, int MAXT, bool SB, int NU, int ND, bool SLOTS, int TP>
 int launch(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t st) {
     auto fn = MG_LDS_KERNEL<TPG, BAND, MAXT, SB, NU, ND, SLOTS, TP>;
     MG_TRY(allow_lds((const void*)fn, 160 * 1024));
     hipLaunchKernelGGL(fn, dim3(B), dim3(L.block), L.lds_bytes, st, a);
     MG_HIP(hipGetLastError());
-    if (L.instance)         // which of the instances below ran (tests: the instance census)
-        *L.instance = TPG | (int64_t)BAND << 8 | (int64_t)SB << 9 | (int64_t)SLOTS << 10 | (int64_t)NU << 11 | (int64_t)ND << 16 |
-                      (int64_t)MAXT << 21 | (int64_t)(TP + 1) << 32;
+    if (L.instance) *L.instance = lds_instance_key(TPG, BAND, MAXT, SB, NU, ND, SLOTS, TP);   // which instance ran (tests: the instance census)
     return MGADMM_OK;
 }
-
-template <int TPG, int MAXT, bool SB>
-int launch_b(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t st) {
-    return a.band ? launch<TPG, true, MAXT, SB>(L, a, B, st) : launch<TPG, false, MAXT, SB>(L, a, B, st);
-}
-
 
 // the instance of this translation unit's kernel for a plan
 int lds_dispatch(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t st) {
@@ -49,65 +58,15 @@ int lds_dispatch(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t st) {
         mg_set_error("lds: launch geometry (J %d, rows %d for %d nodes, %d of %d threads own elements)", a.J, a.NR, a.N, a.nthreads, L.block);
         return MGADMM_ERR_INVALID;
     }
-    if (L.uniform45 && (a.band || L.sb || !((L.tpg == 8 && L.maxt == 1024) || L.tpg == 12))) {
-        mg_set_error("lds: the uniform-row instances exist for TPG 8 (1024-thread class) and TPG 12");
-        return MGADMM_ERR_UNSUPPORTED;
+    switch (L.key) {
+#define MG_LDS_CASE(...) case lds_instance_key(__VA_ARGS__): return launch<__VA_ARGS__>(L, a, B, st);
+        MG_LDS_INSTANCES(MG_LDS_CASE)
+#undef MG_LDS_CASE
     }
-    if (L.uniform45 && L.tpg == 12 && L.maxt == 1024) {        // 342 .. 512 nodes: two time groups in a workgroup of up to 1024 threads (no room for slots)
-        if (L.slots) { mg_set_error("lds: no slot instance in the 1024-thread class of TPG 12"); return MGADMM_ERR_UNSUPPORTED; }
-        switch (a.tail_pairs) {
-            case 0: return launch<12, false, 1024, false, 4, 5, false, 0>(L, a, B, st);
-            case 1: return launch<12, false, 1024, false, 4, 5, false, 1>(L, a, B, st);
-            case 2: return launch<12, false, 1024, false, 4, 5, false, 2>(L, a, B, st);
-            case 3: return launch<12, false, 1024, false, 4, 5, false, 3>(L, a, B, st);
-        }
-        return launch<12, false, 1024, false, 4, 5, false, -1>(L, a, B, st);        // longer tails: pair count at run time
-    }
-    if (L.uniform45 && L.tpg == 12) {
-        switch (a.tail_pairs * 2 + (L.slots ? 1 : 0)) {
-            case 0: return launch<12, false, 640, false, 4, 5, false, 0>(L, a, B, st);
-            case 1: return launch<12, false, 640, false, 4, 5, true, 0>(L, a, B, st);
-            case 2: return launch<12, false, 640, false, 4, 5, false, 1>(L, a, B, st);
-            case 3: return launch<12, false, 640, false, 4, 5, true, 1>(L, a, B, st);
-            case 4: return launch<12, false, 640, false, 4, 5, false, 2>(L, a, B, st);
-            case 5: return launch<12, false, 640, false, 4, 5, true, 2>(L, a, B, st);
-            case 6: return launch<12, false, 640, false, 4, 5, false, 3>(L, a, B, st);
-            case 7: return launch<12, false, 640, false, 4, 5, true, 3>(L, a, B, st);
-        }
-        return L.slots ? launch<12, false, 640, false, 4, 5, true, -1>(L, a, B, st) : launch<12, false, 640, false, 4, 5, false, -1>(L, a, B, st);
-    }
-    if (L.sb) {
-        if (L.tpg == 12 && L.maxt == 640) return launch_b<12, 640, true>(L, a, B, st);
-        if (L.tpg == 8 && L.maxt == 1024) return launch_b<8, 1024, true>(L, a, B, st);
-        mg_set_error("lds: single-buffer mode exists for TPG 12 (<= 640 threads) and TPG 8 only");
-        return MGADMM_ERR_UNSUPPORTED;
-    }
-    if (L.maxt == 640 && L.tpg == 12) return launch_b<12, 640, false>(L, a, B, st);
-    switch (L.tpg) {
-        case 1: return launch_b<1, 1024, false>(L, a, B, st);
-        case 2: return launch_b<2, 1024, false>(L, a, B, st);
-        case 3: return launch_b<3, 1024, false>(L, a, B, st);
-        case 4: return launch_b<4, 1024, false>(L, a, B, st);
-        case 6: return launch_b<6, 1024, false>(L, a, B, st);
-        case 8:
-            if (L.uniform45 && !a.band) {       // uniform-row instances: the pair count of the W_d^T tail table is a compile-time constant
-                switch (a.tail_pairs * 2 + (L.slots ? 1 : 0)) {
-                    case 0: return launch<8, false, 1024, false, 4, 5, false, 0>(L, a, B, st);
-                    case 1: return launch<8, false, 1024, false, 4, 5, true, 0>(L, a, B, st);
-                    case 2: return launch<8, false, 1024, false, 4, 5, false, 1>(L, a, B, st);
-                    case 3: return launch<8, false, 1024, false, 4, 5, true, 1>(L, a, B, st);
-                    case 4: return launch<8, false, 1024, false, 4, 5, false, 2>(L, a, B, st);
-                    case 5: return launch<8, false, 1024, false, 4, 5, true, 2>(L, a, B, st);
-                    case 6: return launch<8, false, 1024, false, 4, 5, false, 3>(L, a, B, st);
-                    case 7: return launch<8, false, 1024, false, 4, 5, true, 3>(L, a, B, st);
-                }
-                // longer tails: pair count at run time
-                return L.slots ? launch<8, false, 1024, false, 4, 5, true, -1>(L, a, B, st) : launch<8, false, 1024, false, 4, 5, false, -1>(L, a, B, st);
-            }
-            return launch_b<8, 1024, false>(L, a, B, st);
-        case 12: return launch_b<12, 1024, false>(L, a, B, st);
-    }
-    mg_set_error("lds: no kernel for TPG %d", L.tpg);
+    const int64_t k = L.key;        // the planner asked for a combination that is not shipped
+    mg_set_error("lds: no k_admm_lds instance for <TPG %d, band %d, MAXT %d, SB %d, NU %d, ND %d, slots %d, TP %d>", (int)(k & 0xFF),
+                 (int)(k >> 8 & 1), (int)(k >> 21 & 0x7FF), (int)(k >> 9 & 1), (int)(k >> 11 & 0x1F), (int)(k >> 16 & 0x1F),
+                 (int)(k >> 10 & 1), (int)(k >> 32 & 0xFF) - 1);
     return MGADMM_ERR_UNSUPPORTED;
 }
 

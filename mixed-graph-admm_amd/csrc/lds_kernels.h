@@ -641,7 +641,7 @@ __device__ __forceinline__ void slot_get(const float* S, int tid, int nthr, floa
 // Callers separate successive calls by barriers.  R: the thread's table rows in registers (uniform instances).
 //
 // FOLD (the cLdr operator of the uniform-row instances): returns v . A v of the WHOLE SAMPLE instead, without a barrier of its
-// own.  A = diag(dc) + c2 Ldr^T Ldr and the second gather uses the exact transpose of W_d (plan_lds gives a graph with
+// own.  A = diag(dc) + c2 Ldr^T Ldr and the second gather uses the exact transpose of W_d (ldsplan::make gives a graph with
 // transpose_by_gather no uniform instance), so v . A v = sum dc_k v_k^2 + c2 sum q_k^2 with q = Ldr v: every q_k has one
 // owner (ghosts and time T hold zeros), and the thread knows its share BEFORE it stores q.  The wave total goes to `red` next
 // to the q store, the barrier that publishes q publishes it too, and the 16 totals are read under the W_d^T gather.  The

@@ -1,6 +1,6 @@
 // Row plan of the uniform-row instances of k_admm_lds (lds_kernels.h) with a compile-time tail: which node a thread owns, and
 // how many positions of the padded W_d^T table each wave gathers.  Plain C++, no HIP: compiled into libmgadmm.so
-// (Engine::plan_lds) and into the CPU check tests/cpu/lds_rows_check.cpp.
+// (ldsplan::make, lds_plan.h) and into the CPU check tests/cpu/lds_rows_check.cpp.
 //
 // The W_d^T table has one width for every row (LDS_NLEAD register entries + 2 * tail_pairs tail entries); a row with fewer
 // off-diagonal entries is padded with {own row, weight 0}.  A wave can skip a position only when it is a pad for ALL of its

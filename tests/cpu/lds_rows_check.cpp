@@ -14,7 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
-#include "lds_rows.h"
+#include "lds_plan.h"       // lds_rows.h; tail_pairs / table_width as the planner computes them
 
 struct Csr {
     std::vector<int> rowptr, col;
@@ -59,8 +59,8 @@ int main(int argc, char** argv) {
     std::vector<int> deg(N);
     int maxdeg = 0;
     for (int i = 0; i < N; ++i) { deg[i] = wt.rowptr[i + 1] - wt.rowptr[i]; maxdeg = std::max(maxdeg, deg[i]); }
-    const int tp = (std::max(0, maxdeg - q.nlead) + 1) / 2;
-    const int WT = q.nlead + 2 * tp;
+    const int tp = ldsplan::tail_pairs(maxdeg, q.nlead);
+    const int WT = ldsplan::table_width(tp, q.nlead);
     const int nw = (N * G + 63) / 64;
 
     const ldsrows::Plan p = ldsrows::make_plan(deg, G, WT, order, q.nlead);

@@ -2,7 +2,7 @@
 that reaches it, and the graph builders those problems use.
 
 Every row names the instance string `nm -C` prints for its kernel and the problem that makes the planner
-(csrc/engine.h, plan_lds) pick it: N, T, t_in, graph kind, the largest W_d^T in-degree of the graph, ablation, task and
+(csrc/lds_plan.h) pick it: N, T, t_in, graph kind, the largest W_d^T in-degree of the graph, ablation, task and
 batch.  tests/test_lds_census_cpu.py checks that the rows cover exactly the shipped instances and that the graphs have
 the stated in-degrees; tests/test_gpu_lds_census.py runs every row against the float64 oracle and asserts the instance
 the solver reports it ran (MGADMM_Q_LDS_INSTANCE).
@@ -22,7 +22,7 @@ Graph kinds:
 import numpy as np
 import torch
 
-NLEAD = 5           # W_d^T entries per row held in registers by k_admm_lds (csrc/lds_args.h, LDS_NLEAD)
+NLEAD = 5           # W_d^T entries per row held in registers by k_admm_lds (csrc/lds_consts.h, LDS_NLEAD)
 
 
 def inst(tpg, band, maxt, sb, nu=0, nd=0, slots=False, tp=-1):
@@ -35,7 +35,7 @@ def uni(tpg, maxt, slots, tp):
 
 
 def tail_pairs(indeg):
-    """Pairs of the padded W_d^T tail table for a largest off-diagonal in-degree `indeg` (plan_lds)."""
+    """Pairs of the padded W_d^T tail table for a largest off-diagonal in-degree `indeg` (csrc/lds_plan.h, tail_pairs)."""
     return (max(0, indeg - NLEAD) + 1) // 2
 
 

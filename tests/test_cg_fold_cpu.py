@@ -6,8 +6,8 @@ transpose of Ldr.  On the float64 oracle:
   * kNN and line / skip graphs, with the reference's quirks on and off (Q1 adds the identity on the t = 0 block of Ldr^T, where
     Ldr p is zero): the two sides agree to 1e-12 relative;
   * mode="physical" (use_kNN=False, quirk Q4: the second operator gathers with W_d itself) on an unpadded k = 4 table: they do
-    NOT agree, so plan_lds must never give such a graph a uniform-row (folded) instance -- the GPU side of this is
-    tests/test_gpu_lds_cg_fold.py.
+    NOT agree, so the planner (csrc/lds_plan.h) must never give such a graph a uniform-row (folded) instance:
+    tests/test_lds_plan_cpu.py asserts that on the planner itself, tests/test_gpu_lds_cg_fold.py on the GPU.
 """
 import numpy as np
 import pytest
