@@ -222,9 +222,12 @@ typedef enum {
     MGADMM_Q_LDS_CG_BARRIERS = 17,/* workgroup barriers per CG iteration of a cLdr solve (x, zd) in the planned k_admm_lds
                                    instance: 4 (5 in single-buffer mode), or 3 in the uniform-row instances, which form p.Ap
                                    from q.q ahead of the q exchange; 0 without the LDS path                              */
-    MGADMM_Q_LDS_INSTANCE = 16  /* template arguments <TPG, BAND, MAXT, SB, NU, ND, SLOTS, TP> of the k_admm_lds instance the
+    MGADMM_Q_LDS_INSTANCE = 16, /* template arguments <TPG, BAND, MAXT, SB, NU, ND, SLOTS, TP> of the k_admm_lds instance the
                                    last LDS launch ran, packed: bits 0-7 TPG, 8 BAND, 9 SB, 10 SLOTS, 11-15 NU, 16-20 ND,
                                    21-31 MAXT, 32-39 TP + 1; -1 before the first launch                                   */
+    MGADMM_Q_LDS_UNIT = 18      /* which of the three compilations of the instances the last LDS launch ran: 0 = k_admm_lds,
+                                   1 = k_admm_lds_ps (per-sample stop test), 2 = k_admm_lds_pp (per-sample weights); -1 before
+                                   the first launch                                                                       */
 } mgadmm_query_t;
 int mgadmm_solver_query(const mgadmm_solver* s, int32_t what, int64_t* out);
 

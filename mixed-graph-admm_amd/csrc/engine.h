@@ -104,6 +104,7 @@ struct Engine : EngineBase {
     LdsSampleParams* d_sp = nullptr;   // [Bmax]
     std::vector<float*> lds_ring_extra;   // iterate buffers beyond the 15 workspace vectors (chunks longer than 4 iterations)
     int64_t lds_instance = -1;       // MGADMM_Q_LDS_INSTANCE: template arguments of the k_admm_lds instance of the last launch
+    int lds_unit = -1;               // MGADMM_Q_LDS_UNIT: which compilation of the instances it came from (0 / 1 / 2 = k_admm_lds / _ps / _pp)
     int lds_chunk = LDS_MAXJ_POOL;   // MGADMM_LDS_CHUNK: ADMM iterations per k_admm_lds launch when the iteration count is fixed (1 .. LDS_MAXJ_POOL)
     hipStream_t st_side = nullptr;
     hipEvent_t ev_main[LDS_NBOUND] = {nullptr}, ev_side[LDS_NBOUND] = {nullptr};
@@ -624,6 +625,7 @@ struct Engine : EngineBase {
             case MGADMM_Q_LDS_ROWS: *out = lds.NR; break;
             case MGADMM_Q_CLDR_SLOTS: *out = cldr_dev.state == 1 ? cl_gt : 0; break;      // (prepared by the first operator application)
             case MGADMM_Q_LDS_INSTANCE: *out = lds_instance; break;
+            case MGADMM_Q_LDS_UNIT: *out = lds_unit; break;
             case MGADMM_Q_LDS_CG_BARRIERS: *out = lds.ok ? lds.cg_barriers : 0; break;
             case MGADMM_Q_NNZ_U: *out = g->hWu.nnz(); break;
             case MGADMM_Q_NNZ_D: *out = g->hWd.nnz(); break;
@@ -1505,7 +1507,7 @@ struct Engine : EngineBase {
 
     int launch_lds(const LdsArgs& a, int B) {
         const bool timed = prof_open(0, 0.0);
-        LdsLaunch L{lds.instance, lds.block, lds.lds_bytes, &lds_instance};
+        LdsLaunch L{lds.instance, lds.block, lds.lds_bytes, &lds_instance, &lds_unit};
         const int rc = mg_lds_iteration(L, a, B, st);
         if (timed) prof_close();
         return rc;

@@ -79,6 +79,8 @@ struct LdsLaunch {
     int block;      // threads per workgroup
     size_t lds_bytes;
     int64_t* instance;  // receives the packed template arguments of the instance launched (MGADMM_Q_LDS_INSTANCE), or nullptr
+    int* unit;          // receives the translation unit whose kernel was launched (MGADMM_Q_LDS_UNIT: 0 k_admm_lds, 1 k_admm_lds_ps,
+                        // 2 k_admm_lds_pp), or nullptr
 };
 
 // J ADMM iterations for B samples (one workgroup per sample); returns a mgadmm_status

@@ -9,6 +9,10 @@
 #include <cstdint>
 #include "lds_kernels.h"
 
+#ifndef MG_LDS_UNIT
+#error "MG_LDS_UNIT: the translation unit that includes lds_dispatch.h says which kernels it compiles (MGADMM_Q_LDS_UNIT)"
+#endif
+
 namespace {
 
 std::mutex g_attr_mu;
@@ -49,6 +53,7 @@ int launch(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t st) {
     hipLaunchKernelGGL(fn, dim3(B), dim3(L.block), L.lds_bytes, st, a);
     MG_HIP(hipGetLastError());
     if (L.instance) *L.instance = lds_instance_key(TPG, BAND, MAXT, SB, NU, ND, SLOTS, TP);   // which instance ran (tests: the instance census)
+    if (L.unit) *L.unit = MG_LDS_UNIT;      // ... of which translation unit (defined beside MG_LDS_KERNEL by the file that includes this one)
     return MGADMM_OK;
 }
 

@@ -1,4 +1,5 @@
 // LDS-resident fused ADMM path: kernel instantiations and launches (own translation unit: the library builds in parallel).
+#define MG_LDS_UNIT 0     // MGADMM_Q_LDS_UNIT: this unit's launches report the kernels k_admm_lds
 #include "lds_dispatch.h"
 
 int mg_lds_iteration(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t st) {

@@ -2,6 +2,7 @@
 // kernels k_admm_lds_pp.  The per-sample stop test is compiled in as well and runs when the launch carries stop words.  Own
 // translation unit: it compiles beside lds_launch.hip and lds_launch_ps.hip, whose instances stay what they were.
 #define MGADMM_LDS_PER_SAMPLE_PARAMS 1
+#define MG_LDS_UNIT 2     // MGADMM_Q_LDS_UNIT: this unit's launches report the kernels k_admm_lds_pp
 #include "lds_dispatch.h"
 
 int mg_lds_iteration_pp(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t st) { return lds_dispatch(L, a, B, st); }

@@ -29,7 +29,9 @@ NMETRIC = 11
  M_RECOVER) = range(11)
 NPROF = 4
 (Q_LDS_OK, Q_LDS_TPG, Q_LDS_THREADS, Q_LDS_BYTES, Q_LDS_ROW_STRIDE, Q_NNZ_U, Q_NNZ_D, Q_NNZ_DT, Q_TILE_ROWS, Q_LDS_UNIFORM,
- Q_LDS_TAIL_PAIRS, Q_LDS_LEAD, Q_LDS_SLOTS, Q_LDS_CHUNK, Q_LDS_ROWS, Q_CLDR_SLOTS, Q_LDS_INSTANCE, Q_LDS_CG_BARRIERS) = range(18)
+ Q_LDS_TAIL_PAIRS, Q_LDS_LEAD, Q_LDS_SLOTS, Q_LDS_CHUNK, Q_LDS_ROWS, Q_CLDR_SLOTS, Q_LDS_INSTANCE, Q_LDS_CG_BARRIERS,
+ Q_LDS_UNIT) = range(19)
+LDS_UNITS = ("k_admm_lds", "k_admm_lds_ps", "k_admm_lds_pp")      # values of Q_LDS_UNIT (-1: no LDS launch yet)
 
 _i32p = C.POINTER(C.c_int32)
 _f32p = C.POINTER(C.c_float)

@@ -271,3 +271,84 @@ def tables_for(r, seed=0):
         cl = _ring(N, 4)
         return torch.from_numpy(cl), torch.from_numpy(_distances(cl, seed))
     return None
+
+
+# ------------------------------------------------------------------- census of the other two compilations of the instances
+# The library compiles the instances three times: k_admm_lds (csrc/lds_launch.hip), k_admm_lds_ps with the per-sample stop test
+# (lds_launch_ps.hip) and k_admm_lds_pp with per-sample weights (lds_launch_pp.hip).  tests/test_gpu_lds_census_units.py runs
+# every census row through the last two and compares with the B = 1 solves of the first, bit for bit.  The constants and the
+# tolerance picker of that test (plain numpy: tests/test_lds_census_cpu.py checks the picker on hand-made tables).
+UNITS = ("ps", "pp")
+UNIT_K = 12         # ADMM iterations of a row
+UNIT_CHUNK = 4      # MGADMM_LDS_CHUNK of the batch solves: launch boundaries fall inside the K iterations
+UNIT_MARGIN = 0.01  # no deciding residual within 1 % of the tolerance
+# Rows that cannot meet the picker's conditions with K = 12 and the scales 0.5 + 1.5 b / (B - 1), {instance: dict(K=.., scales=..)}:
+# their residuals fall by 6 .. 9 % per iteration from the third on, so a sample four times another does not come below the other's
+# second residual within 12 iterations; with the scales 1 + b / (B - 1) (a factor of two) it does.
+_NARROW = lambda B: 1.0 + np.arange(B) / (B - 1)
+UNIT_OVERRIDES = {
+    uni(8, 1024, False, 0): dict(scales=_NARROW(70)),
+    uni(8, 1024, False, 1): dict(scales=_NARROW(3)),
+    uni(8, 1024, False, -1): dict(scales=_NARROW(3)),
+    uni(12, 640, True, 1): dict(scales=_NARROW(3)),
+    uni(12, 640, False, -1): dict(scales=_NARROW(3)),
+    inst(12, True, 640, True): dict(scales=_NARROW(3)),
+}
+
+
+def unit_k(r):
+    return UNIT_OVERRIDES.get(r["expect"], {}).get("K", UNIT_K)
+
+
+def unit_scales(r):
+    """Factor of every sample's input: the samples converge at different iterations."""
+    B = r["B"]
+    s = UNIT_OVERRIDES.get(r["expect"], {}).get("scales")
+    return 0.5 + 1.5 * np.arange(B) / (B - 1) if s is None else np.asarray(s, dtype=np.float64)
+
+
+def unit_picks(r):
+    return [0, r["B"] // 2, r["B"] - 1]
+
+
+def stop_iterations(res, tol, K, chunk=UNIT_CHUNK, margin=UNIT_MARGIN):
+    """First crossing n_b (iterations run, 1-based) of every row of `res` (picks, K) -- the residual that decides the stop test
+    after each iteration -- under the tolerance `tol`.  Asserts what makes the tolerance a test of per-sample stopping:
+    every n_b in [2, K - 1]; at least two distinct n_b; two picks stop in different launches of `chunk` iterations; no residual
+    of a pick up to its n_b within `margin` of the tolerance (no stop is a rounding decision)."""
+    res = np.asarray(res, dtype=np.float64)
+    assert res.ndim == 2 and res.shape[1] == K and np.isfinite(res).all() and tol > 0, (res.shape, K, tol)
+    n = []
+    for b, row in enumerate(res):
+        below = np.nonzero(row < tol)[0]
+        assert below.size, f"pick {b} never falls below {tol!r} in {K} iterations"
+        n.append(int(below[0]) + 1)
+    assert all(2 <= v <= K - 1 for v in n), f"first crossings {n} not all in [2, {K - 1}] at {tol!r}"
+    assert len(set(n)) >= 2, f"every pick stops at iteration {n[0]} at {tol!r}"
+    assert len({-(-v // chunk) for v in n}) >= 2, f"first crossings {n}: every pick stops in the same launch of {chunk} at {tol!r}"
+    for b, (row, v) in enumerate(zip(res, n)):
+        near = np.abs(row[:v] / tol - 1.0) <= margin
+        assert not near.any(), f"pick {b}: residual {row[:v][near][0]!r} of iteration {int(np.nonzero(near)[0][0]) + 1} within {margin} of {tol!r}"
+    return n
+
+
+def pick_admm_tol(res, K, chunk=UNIT_CHUNK, margin=UNIT_MARGIN):
+    """(ADMM_tol, [n_b]) for a table `res` (picks, K) of deciding residuals: among the geometric means of neighbouring table
+    values, the one that meets the conditions of stop_iterations with the most launches stopped in, then the most distinct
+    n_b, then the widest gap to the nearest residual.  Raises AssertionError when no tolerance meets them."""
+    res = np.asarray(res, dtype=np.float64)
+    assert res.ndim == 2 and res.shape[1] == K and np.isfinite(res).all() and (res > 0).all(), (res.shape, K)
+    vals = np.unique(res)
+    best, why = None, "a table of one value"
+    for tol in np.sqrt(vals[:-1] * vals[1:]):
+        try:
+            n = stop_iterations(res, tol, K, chunk, margin)
+        except AssertionError as e:
+            why = str(e)
+            continue
+        gap = min(float(np.abs(np.log(row[:v] / tol)).min()) for row, v in zip(res, n))
+        score = (len({-(-v // chunk) for v in n}), len(set(n)), gap)
+        if best is None or score > best[0]:
+            best = (score, float(tol))
+    assert best is not None, f"no tolerance meets the stop conditions (last candidate: {why})"
+    return best[1], stop_iterations(res, best[1], K, chunk, margin)
