@@ -15,6 +15,7 @@
 #include "stream_kernels.h"
 #include "lds_args.h"
 #include "lds_plan.h"
+#include "lds_schedule.h"
 
 namespace {
 
@@ -32,10 +33,6 @@ enum VecId {
 constexpr int LAG = 2;          // CG iterations enqueued ahead of the host's convergence check
 constexpr int NRED_MAX = 6;
 constexpr int PROF_POOL = 32768;
-constexpr int LDS_SETS = 3;             // interior iterate-buffer sets / per-sample metric sets of the chunked schedule (chunks in flight)
-constexpr int LDS_NBOUND = 4;           // iterate buffers at the chunk boundaries
-constexpr int LDS_MAXJ_POOL = LDS_MAXJ;   // longest chunk of the LDS path's chunked schedule: LDS_SETS (J - 1) + LDS_NBOUND iterate buffers -- 15
-                                          // out of the workspace (enough for J = 4), the rest allocated on the first solve that asks for a longer chunk
 constexpr int NACT_LOG = 1 << 16;   // pinned log of the per-iteration active-sample counts (one int per CG iteration enqueued)
 
 template <typename S>
@@ -102,10 +99,15 @@ struct Engine : EngineBase {
     int sp_B = 0;                 // samples of the table; 0 = none set
     std::vector<double> sp_val[6];   // rho, rho_u, rho_d, mu_u, mu_d1, mu_d2
     LdsSampleParams* d_sp = nullptr;   // [Bmax]
-    std::vector<float*> lds_ring_extra;   // iterate buffers beyond the 15 workspace vectors (chunks longer than 4 iterations)
+    // iterate buffers of solve_lds by slot number (lds_schedule.h): the 15 workspace vectors this path does not use otherwise
+    // hold the LDS_SETS (J - 1) + LDS_NBOUND = 13 slots of J = 4; chunks longer than 4 iterations (up to LDS_MAXJ) get the
+    // rest in lds_ring_extra on the first solve that asks for them, kept for the solver's lifetime
+    static constexpr int ring_ids[] = {V_XA, V_XB, V_ZUB, V_ZDB, V_PHIB, V_Y, V_MASK, V_R, V_P, V_Q, V_AP, V_RHS, V_TMP, V_IO0, V_IO1};
+    static constexpr int NRING = (int)(sizeof(ring_ids) / sizeof(ring_ids[0]));
+    std::vector<float*> lds_ring_extra;
     int64_t lds_instance = -1;       // MGADMM_Q_LDS_INSTANCE: template arguments of the k_admm_lds instance of the last launch
     int lds_unit = -1;               // MGADMM_Q_LDS_UNIT: which compilation of the instances it came from (0 / 1 / 2 = k_admm_lds / _ps / _pp)
-    int lds_chunk = LDS_MAXJ_POOL;   // MGADMM_LDS_CHUNK: ADMM iterations per k_admm_lds launch when the iteration count is fixed (1 .. LDS_MAXJ_POOL)
+    int lds_chunk = LDS_MAXJ;   // MGADMM_LDS_CHUNK: ADMM iterations per k_admm_lds launch when the iteration count is fixed (1 .. LDS_MAXJ)
     hipStream_t st_side = nullptr;
     hipEvent_t ev_main[LDS_NBOUND] = {nullptr}, ev_side[LDS_NBOUND] = {nullptr};
     // profiling
@@ -450,7 +452,7 @@ struct Engine : EngineBase {
         if (const char* e = getenv("MGADMM_SWEEP_REV")) sweep_rev = atoi(e);
         if (const char* e = getenv("MGADMM_CLDR_ORDER")) cldr_tile_major = atoi(e);
         if (const char* e = getenv("MGADMM_LDS_ASYNC")) lds_async = atoi(e);
-        if (const char* e = getenv("MGADMM_LDS_CHUNK")) lds_chunk = std::max(1, std::min(atoi(e), LDS_MAXJ_POOL));
+        if (const char* e = getenv("MGADMM_LDS_CHUNK")) lds_chunk = std::max(1, std::min(atoi(e), LDS_MAXJ));
         Geom q = make_geom(Bmax);
         Bp_max = q.Bp;
         // Bp for smaller batches never exceeds Bp_max rounded to 256
@@ -621,7 +623,7 @@ struct Engine : EngineBase {
             case MGADMM_Q_LDS_TAIL_PAIRS: *out = lds.tail_pairs; break;
             case MGADMM_Q_LDS_LEAD: *out = LDS_NLEAD; break;
             case MGADMM_Q_LDS_SLOTS: *out = lds.slots; break;
-            case MGADMM_Q_LDS_CHUNK: *out = std::max(1, std::min(lds_chunk, LDS_MAXJ_POOL)); break;
+            case MGADMM_Q_LDS_CHUNK: *out = std::max(1, std::min(lds_chunk, LDS_MAXJ)); break;
             case MGADMM_Q_LDS_ROWS: *out = lds.NR; break;
             case MGADMM_Q_CLDR_SLOTS: *out = cldr_dev.state == 1 ? cl_gt : 0; break;      // (prepared by the first operator application)
             case MGADMM_Q_LDS_INSTANCE: *out = lds_instance; break;
@@ -1179,6 +1181,39 @@ struct Engine : EngineBase {
         return MGADMM_OK;
     }
 
+    // device buffer that grows on demand; a failed allocation leaves it empty
+    template <class E>
+    int grow(E*& buf, size_t& elems, size_t need) {
+        if (need <= elems) return MGADMM_OK;
+        if (buf) MG_HIP(hipFree(buf));
+        buf = nullptr;
+        elems = 0;
+        MG_HIP(hipMalloc(&buf, need * sizeof(E)));
+        elems = need;
+        return MGADMM_OK;
+    }
+    // per-sample metric history of a solve, when the caller asks for it
+    int ensure_hist_ps(const mgadmm_history* hist, int B) {
+        if (!hist || !hist->metrics_per_sample) return MGADMM_OK;
+        return grow(d_hist_ps, hist_ps_elems, (size_t)p.max_admm_iter * MGADMM_NMETRIC * B);
+    }
+    // The host's stop test after iteration `it` (ADMM.py:645-646): copies the metric row and the non-finite flag, waits for
+    // the stream, and sets *stop when the loop ends here: both residual maxima are below admm_tol, or a NaN / Inf was met
+    // (*rc_final = MGADMM_ERR_NONFINITE)
+    int host_stop_test(int it, bool has_phi, bool has_zd, bool* stop, int* rc_final) {
+        MG_HIP(hipMemcpyAsync(h_row, d_hist + (size_t)it * MGADMM_NMETRIC, sizeof(double) * MGADMM_NMETRIC, hipMemcpyDeviceToHost, st));
+        MG_HIP(hipMemcpyAsync(h_flag, d_nonfinite, sizeof(int), hipMemcpyDeviceToHost, st));
+        MG_HIP(hipStreamSynchronize(st));
+        bool finite = h_flag[0] == 0;
+        for (int k = 0; k < MGADMM_NMETRIC; ++k) finite = finite && std::isfinite(h_row[k]);
+        if (!finite) { *rc_final = MGADMM_ERR_NONFINITE; *stop = true; return MGADMM_OK; }
+        double pri = h_row[MGADMM_M_PRI_ZU], dual = h_row[MGADMM_M_DUAL_ZU];
+        if (has_phi) { pri = std::max(pri, h_row[MGADMM_M_PRI_PHI]); dual = std::max(dual, h_row[MGADMM_M_DUAL_PHI]); }
+        if (has_zd) { pri = std::max(pri, h_row[MGADMM_M_PRI_ZD]); dual = std::max(dual, h_row[MGADMM_M_DUAL_ZD]); }
+        *stop = pri < p.admm_tol && dual < p.admm_tol;
+        return MGADMM_OK;
+    }
+
     int solve(const void* y, const void* mask, int mask_f32, int B, const void* x0, const mgadmm_state* state_in, void* x_out,
               const mgadmm_state* state_out, mgadmm_history* hist, hipStream_t s) override {
         MG_TRY(check_B(B, "solve"));
@@ -1201,15 +1236,7 @@ struct Engine : EngineBase {
         const int max_it = p.max_admm_iter;
         const bool record = p.record_cg_coeffs && hist && hist->cg_alpha && hist->cg_beta;
 
-        if (hist && hist->metrics_per_sample) {
-            size_t need = (size_t)max_it * MGADMM_NMETRIC * B;
-            if (need > hist_ps_elems) {
-                if (d_hist_ps) MG_HIP(hipFree(d_hist_ps));
-                d_hist_ps = nullptr;
-                MG_HIP(hipMalloc(&d_hist_ps, need * sizeof(double)));
-                hist_ps_elems = need;
-            }
-        }
+        MG_TRY(ensure_hist_ps(hist, B));
         MG_HIP(hipMemsetAsync(d_nonfinite, 0, sizeof(int), st));
         MG_HIP(hipMemsetAsync(d_ps, 0, sizeof(double) * MGADMM_NMETRIC * q.Bp, st));
         MG_HIP(hipMemsetAsync(d_cg_iters, 0, sizeof(int) * (size_t)max_it * 3 * q.Bp, st));
@@ -1313,17 +1340,9 @@ struct Engine : EngineBase {
             if (has_phi) std::swap(phc, phn);
             n_done = it + 1;
             if (p.check_stop) {
-                MG_HIP(hipMemcpyAsync(h_row, d_hist + (size_t)it * MGADMM_NMETRIC, sizeof(double) * MGADMM_NMETRIC,
-                                      hipMemcpyDeviceToHost, st));
-                MG_HIP(hipMemcpyAsync(h_flag, d_nonfinite, sizeof(int), hipMemcpyDeviceToHost, st));
-                MG_HIP(hipStreamSynchronize(st));
-                bool finite = h_flag[0] == 0;
-                for (int k = 0; k < MGADMM_NMETRIC; ++k) finite = finite && std::isfinite(h_row[k]);
-                if (!finite) { rc_final = MGADMM_ERR_NONFINITE; break; }
-                double pri = h_row[MGADMM_M_PRI_ZU], dual = h_row[MGADMM_M_DUAL_ZU];
-                if (has_phi) { pri = std::max(pri, h_row[MGADMM_M_PRI_PHI]); dual = std::max(dual, h_row[MGADMM_M_DUAL_PHI]); }
-                if (has_zd) { pri = std::max(pri, h_row[MGADMM_M_PRI_ZD]); dual = std::max(dual, h_row[MGADMM_M_DUAL_ZD]); }
-                if (pri < p.admm_tol && dual < p.admm_tol) break;      // ADMM.py:645-646
+                bool stop = false;
+                MG_TRY(host_stop_test(it, has_phi, has_zd, &stop, &rc_final));
+                if (stop) break;
             }
         }
         // ---- results
@@ -1486,7 +1505,7 @@ struct Engine : EngineBase {
         MG_HIP(hipMalloc(&d_m2, sizeof(double) * T * N * (1 + (size_t)(Bmax + 63) / 64)));
         MG_HIP(hipMalloc(&d_stop, sizeof(int)));
         MG_HIP(hipMemset(d_stop, 0, sizeof(int)));
-        MG_HIP(hipMalloc(&d_ps_ring, sizeof(double) * LDS_SETS * LDS_MAXJ_POOL * MGADMM_NMETRIC * Bp_max));
+        MG_HIP(hipMalloc(&d_ps_ring, sizeof(double) * LDS_SETS * LDS_MAXJ * MGADMM_NMETRIC * Bp_max));
         MG_HIP(hipMalloc(&d_pstop, sizeof(int) * (2 * (size_t)Bp_max + 1)));
         {
             // helper stream of the overlapped outer loop: non-blocking (the caller's stream may be the legacy default stream,
@@ -1513,295 +1532,285 @@ struct Engine : EngineBase {
         return rc;
     }
 
+    // ---------------------------------------------------------------- solve_lds: one solve on the LDS path
+    struct LdsRun {                       // what the members below share
+        ldssched::Schedule s;
+        LdsArgs a;
+        int B, Bp;
+        bool has_phi, has_zd, record, cold;   // cold: no warm-start state
+        float* xo;                        // the caller's x_out
+        mgadmm_history* hist;
+        int n_done = 0, rc = MGADMM_OK;
+    };
+
+    // buffer of an iterate slot; slots beyond the workspace vectors are allocated here
+    int lds_ring_reserve(int slots) {
+        while (NRING + (int)lds_ring_extra.size() < slots) {
+            float* b = nullptr;
+            MG_HIP(hipMalloc(&b, vec_elems * sizeof(S)));
+            lds_ring_extra.push_back(b);
+            ws_bytes += (int64_t)(vec_elems * sizeof(S));
+        }
+        return MGADMM_OK;
+    }
+    float* lds_ring(int slot) const { return slot < NRING ? (float*)vec[ring_ids[slot]] : lds_ring_extra[slot - NRING]; }
+    // iterate k (k = 0: the initial guess)
+    float* lds_xbuf(const LdsRun& r, int k) const {
+        const int slot = r.s.slot_of_iterate(k);
+        return slot == ldssched::X_OUT ? r.xo : lds_ring(slot);
+    }
+
+    // the part of the launch arguments that no schedule changes.  zu, zd, phi and the dual variables: workspace vectors in the
+    // kernel's thread-major layout (lds_kernels.h, lds_state_index)
+    void lds_fill_args(LdsRun& r, const void* y, const void* mask) const {
+        LdsArgs& a = r.a;
+        a = LdsArgs{};
+        a.T = T; a.N = N; a.TN = T * N; a.TS = lds.TS; a.t_in = p.t_in; a.G = lds.G; a.B = r.B; a.Bp = r.Bp;
+        a.nthreads = lds.nthreads; a.NR = lds.NR; a.tail_pairs = lds.tail_pairs;
+        a.has_phi = r.has_phi; a.has_zd = r.has_zd;
+        const LhsDef dx = lhs_def(MGADMM_LHS_X);
+        a.lhsx_kind = dx.kind == 1 ? 1 : 0;
+        a.cx1 = (float)dx.c1; a.cx2 = (float)dx.c2;
+        a.band = g->mode == MGADMM_TEMPORAL_BAND; a.skip = g->skip;
+        a.q1 = a.band ? 0 : g->q1;
+        a.max_cg = p.max_cg_iter; a.record = r.record ? 1 : 0;
+        a.rho = (float)p.rho; a.rho_u = (float)p.rho_u; a.rho_d = (float)p.rho_d;
+        a.mu_u = (float)p.mu_u; a.mu_d1 = (float)p.mu_d1; a.mu_d2 = (float)p.mu_d2;
+        a.cg_tol2 = p.cg_tol * p.cg_tol;
+        a.csr = d_lds_csr; a.lds_img0 = lds.lds_img0; a.lds_img_ints = lds.lds_img_ints;
+        a.off_rp_u = lds.off_rp_u; a.off_rp_d = lds.off_rp_d;
+        a.off_en_u = lds.off_en_u; a.off_en_d = lds.off_en_d; a.off_lead_t = lds.off_lead_t; a.off_tail_t = lds.off_tail_t; a.off_diag = lds.off_diag;
+        a.npos = lds.npos_word; a.off_node = lds.off_node;
+        a.band_w = g->band_w;
+        a.zu = (float*)vec[V_ZUA]; a.zd = (float*)vec[V_ZDA]; a.phi = (float*)vec[V_PHIA];
+        a.gam = (float*)vec[V_GAM]; a.gu = (float*)vec[V_GU]; a.gd = (float*)vec[V_GD];
+        // staggered start (k_admm_lds): only when the launch runs several rounds of workgroups per CU
+        const int ncu = dev_cus > 0 ? dev_cus : 256;
+        int us = 48;
+        if (const char* e = getenv("MGADMM_LDS_STAGGER_US")) us = atoi(e);
+        a.stagger_wgs = ncu;
+        a.stagger_ticks = (r.B >= 2 * ncu && us > 0) ? us * 100 : 0;
+        a.y = (const float*)y; a.mask = (const float*)mask;
+        a.alpha_hist = r.record ? (float*)d_alpha_hist : nullptr; a.beta_hist = r.record ? (float*)d_beta_hist : nullptr;
+        a.nonfinite = d_nonfinite;
+    }
+
+    // iterate 0 and the state: a warm start is converted into the thread-major layout, a cold start forms ADMM.py:528-544
+    int lds_state_in(const LdsRun& r, const void* x0, const mgadmm_state* si) {
+        const LdsArgs& a = r.a;
+        float* const x = lds_xbuf(r, 0);
+        if (!si) {
+            float tm = 0, t2m = 0;
+            for (int t = 0; t < p.t_in; ++t) { tm += (float)t; t2m += (float)t * (float)t; }
+            tm /= (float)p.t_in;
+            t2m /= (float)p.t_in;
+            const float den = t2m - tm * tm;
+            return mg_lds_init(a.mask != nullptr, T, p.t_in, N, lds.TPG, r.B, tm, den, a.y, a.mask, x, a.zu, a.zd, a.gam, a.gu, a.gd,
+                               d_nonfinite, lds_row_of_node(), st);
+        }
+        if (x0 != nullptr && x != x0) MG_HIP(hipMemcpyAsync(x, x0, (size_t)r.B * T * N * sizeof(float), hipMemcpyDeviceToDevice, st));
+        auto in = [&](float* dst, const void* src) {
+            return src == nullptr ? (int)MGADMM_OK : mg_lds_state_layout(true, T, N, lds.TPG, r.B, (const float*)src, dst, lds_row_of_node(), st);
+        };
+        MG_TRY(in(a.zu, si->zu));
+        MG_TRY(in(a.gu, si->gamma_u));
+        MG_TRY(in(a.zd, si->zd));            // the vectors an ablation does not iterate on are carried through
+        MG_TRY(in(a.gd, si->gamma_d));
+        MG_TRY(in(a.phi, si->phi));
+        return in(a.gam, si->gamma);
+    }
+    // the state the caller asked for, in the reference's layout
+    int lds_state_out(const LdsRun& r, const mgadmm_state* so) {
+        const LdsArgs& a = r.a;
+        auto out = [&](void* dst, const float* src) {
+            return dst == nullptr ? (int)MGADMM_OK : mg_lds_state_layout(false, T, N, lds.TPG, r.B, src, (float*)dst, lds_row_of_node(), st);
+        };
+        MG_TRY(out(so->zu, a.zu));
+        MG_TRY(out(so->zd, a.zd));
+        if (r.has_phi) {
+            MG_TRY(out(so->phi, a.phi));
+            MG_TRY(out(so->gamma, a.gam));
+        }
+        MG_TRY(out(so->gamma_u, a.gu));
+        return out(so->gamma_d, a.gd);
+    }
+
+    // the whole-batch metrics of iteration `it` (delta_x_per_step, norms / means over the samples) on stream `s`
+    int lds_batch_metrics(const LdsRun& r, int it, const double* ps, hipStream_t s) {
+        const bool per_sample = r.hist && r.hist->metrics_per_sample;
+        MG_TRY(mg_lds_dxps(T, N, r.B, (const float*)lds_xbuf(r, it + 1), (const float*)lds_xbuf(r, it), d_m2, d_dxps + (size_t)it * T, r.a.stop, s));
+        hipLaunchKernelGGL(k_batch_metrics, dim3(MGADMM_NMETRIC), dim3(256), 0, s, ps, r.Bp, r.B, d_hist + (size_t)it * MGADMM_NMETRIC,
+                           per_sample ? d_hist_ps + (size_t)it * MGADMM_NMETRIC * r.B : nullptr);
+        MG_HIP(hipGetLastError());
+        return MGADMM_OK;
+    }
+
+    // The host's late look at a device word (the stop word, the number of stopped samples): after step `c` the word is copied
+    // to the pinned ring, and *word is what it was after step c - LAG (0 while there is no such step): ldssched::lag_step
+    int lagged_word(int c, const int* d_word, int* word) {
+        const ldssched::LagStep l = ldssched::lag_step(c, LAG);
+        MG_HIP(hipMemcpyAsync(h_flag + 1 + l.put, d_word, sizeof(int), hipMemcpyDeviceToHost, st));
+        MG_HIP(hipEventRecord(ev_ring[l.put], st));
+        *word = 0;
+        if (l.get >= 0) {
+            MG_HIP(hipEventSynchronize(ev_ring[l.get]));
+            *word = h_flag[1 + l.get];
+        }
+        return MGADMM_OK;
+    }
+
+    // CHUNKS: one launch per chunk on the caller's stream; the whole-batch metrics of the chunk on the helper stream, ordered by
+    // the events of lds_schedule.h (per-sample stop: one stream, no metrics, the host ends when every sample has stopped)
+    int lds_run_chunks(LdsRun& r) {
+        LdsArgs& a = r.a;
+        const size_t row = (size_t)MGADMM_NMETRIC * r.Bp;
+        int c = 0;
+        for (; c < r.s.chunks(); ++c) {
+            const ldssched::Chunk ch = r.s.chunk(c);
+            a.first = ch.it0 == 0 && r.cold;      // phi = Ldr x0 is formed by the first iteration of a cold start
+            a.J = ch.Jc;
+            for (int k = 0; k <= ch.Jc; ++k) a.xs[k] = lds_xbuf(r, ch.it0 + k);
+            a.cg_iters = d_cg_iters + (size_t)ch.it0 * 3 * r.Bp;
+            if (r.s.per_sample) {
+                a.ps = d_ps_full + (size_t)ch.it0 * row;
+                a.it0 = ch.it0;
+                MG_TRY(launch_lds(a, r.B));
+                r.n_done = ch.it0 + ch.Jc;
+                int stopped = 0;
+                MG_TRY(lagged_word(c, a.pstop_count, &stopped));
+                if (stopped == r.B) break;        // the launches enqueued since returned at their guards
+                continue;
+            }
+            a.ps = d_ps_ring + (size_t)ch.set * r.s.J * row;
+            if (ch.wait >= 0) MG_HIP(hipStreamWaitEvent(st, ev_side[ch.wait], 0));
+            MG_TRY(launch_lds(a, r.B));
+            MG_HIP(hipEventRecord(ev_main[ch.ev], st));
+            MG_HIP(hipStreamWaitEvent(st_side, ev_main[ch.ev], 0));
+            for (int k = 0; k < ch.Jc; ++k) MG_TRY(lds_batch_metrics(r, ch.it0 + k, a.ps + (size_t)k * row, st_side));
+            MG_HIP(hipEventRecord(ev_side[ch.ev], st_side));
+            r.n_done = ch.it0 + ch.Jc;
+        }
+        if (!r.s.per_sample && r.s.join(c) >= 0) MG_HIP(hipStreamWaitEvent(st, ev_side[r.s.join(c)], 0));
+        return MGADMM_OK;
+    }
+
+    // SYNC and DEVSTOP: one iteration per launch, everything on the caller's stream
+    int lds_run_steps(LdsRun& r) {
+        LdsArgs& a = r.a;
+        const size_t K = p.max_cg_iter;
+        for (int it = 0; it < r.s.max_it; ++it) {
+            a.first = it == 0 && r.cold;          // phi = Ldr x0 is formed by the first launch of a cold start
+            a.J = 1;
+            a.xs[0] = lds_xbuf(r, it); a.xs[1] = lds_xbuf(r, it + 1);
+            a.cg_iters = d_cg_iters + (size_t)it * 3 * r.Bp;
+            a.ps = d_ps;
+            if (r.s.per_sample) { a.ps = d_ps_full + (size_t)it * MGADMM_NMETRIC * r.Bp; a.it0 = it; }
+            if (r.record) {
+                MG_TRY(fill((S*)d_alpha_hist, 3 * K * r.Bp, (S)NAN));
+                MG_TRY(fill((S*)d_beta_hist, 3 * K * r.Bp, (S)NAN));
+            }
+            MG_TRY(launch_lds(a, r.B));
+            if (!r.s.per_sample) MG_TRY(lds_batch_metrics(r, it, a.ps, st));
+            if (r.record) {
+                for (int w = 0; w < 3; ++w) {
+                    if (w == 2 && !r.has_zd) continue;
+                    double* ao = r.hist->cg_alpha + ((size_t)it * 3 + w) * K * r.B;
+                    double* bo = r.hist->cg_beta + ((size_t)it * 3 + w) * K * r.B;
+                    MG_TRY(fetch_hist(d_alpha_hist + (size_t)w * K * r.Bp, K * r.Bp, ao, r.B, r.Bp, K));
+                    MG_TRY(fetch_hist(d_beta_hist + (size_t)w * K * r.Bp, K * r.Bp, bo, r.B, r.Bp, K));
+                }
+            }
+            r.n_done = it + 1;
+            if (r.s.per_sample) {         // (the host is in step with the device here: the count of this very launch)
+                MG_HIP(hipMemcpyAsync(h_flag + 1, a.pstop_count, sizeof(int), hipMemcpyDeviceToHost, st));
+                MG_HIP(hipStreamSynchronize(st));
+                if (h_flag[1] == r.B) break;
+            } else if (r.s.kind == ldssched::DEVSTOP) {
+                int sw = 0;
+                MG_TRY(mg_lds_stop_test(d_hist + (size_t)it * MGADMM_NMETRIC, d_nonfinite, r.has_phi, r.has_zd, p.admm_tol, it, d_stop, st));
+                MG_TRY(lagged_word(it, d_stop, &sw));
+                if (sw != 0) break;       // the launches enqueued since returned at their guards
+            } else if (p.check_stop) {
+                bool stop = false;
+                MG_TRY(host_stop_test(it, r.has_phi, r.has_zd, &stop, &r.rc));
+                if (stop) break;
+            }
+        }
+        if (r.s.kind == ldssched::DEVSTOP) {
+            // the stop word after everything enqueued has run: 0 = no stop (all enqueued iterations ran), k > 0 = the stop
+            // test passed at the end of iteration k - 1, k < 0 = iteration -k - 1 met a NaN / Inf
+            MG_HIP(hipMemcpyAsync(h_flag + 1, d_stop, sizeof(int), hipMemcpyDeviceToHost, st));
+            MG_HIP(hipStreamSynchronize(st));
+            const int sw = h_flag[1];
+            if (sw > 0) r.n_done = sw;
+            else if (sw < 0) { r.n_done = -sw; r.rc = MGADMM_ERR_NONFINITE; }
+        }
+        return MGADMM_OK;
+    }
+
+    // per-sample stop: r.n_done iterations were enqueued; the history from the stop words and the per-sample sums, the
+    // iterations of every sample to `nps`, the largest of them to r.n_done
+    int lds_finish_per_sample(LdsRun& r, std::vector<int>& nps) {
+        int* const d_nps = d_pstop + Bp_max + 1;
+        MG_TRY(mg_lds_ps_history(d_ps_full, d_pstop, r.n_done, r.s.max_it, r.B, r.Bp, d_nps, d_hist,
+                                 (r.hist && r.hist->metrics_per_sample) ? d_hist_ps : nullptr, st));
+        nps.resize(r.B);
+        MG_HIP(hipMemcpyAsync(nps.data(), d_nps, sizeof(int) * r.B, hipMemcpyDeviceToHost, st));
+        MG_HIP(hipStreamSynchronize(st));
+        r.n_done = *std::max_element(nps.begin(), nps.end());
+        return MGADMM_OK;
+    }
+
     int solve_lds(const void* y, const void* mask, int B, const void* x0, const mgadmm_state* state_in, void* x_out,
                   const mgadmm_state* state_out, mgadmm_history* hist) {
         if constexpr (!std::is_same<S, float>::value) {
             return MGADMM_ERR_UNSUPPORTED;
         } else {
-            const int abl = p.ablation;
-            const bool has_phi = (abl == MGADMM_ABL_NONE || abl == MGADMM_ABL_DGLR);
-            const bool has_zd = (abl != MGADMM_ABL_DGLR);
-            const int max_it = p.max_admm_iter;
-            const bool record = p.record_cg_coeffs && hist && hist->cg_alpha && hist->cg_beta;
-            const int Bp = (B + 63) / 64 * 64;
-            const size_t TN = (size_t)T * N;
-            if (hist && hist->metrics_per_sample) {
-                size_t need = (size_t)max_it * MGADMM_NMETRIC * B;
-                if (need > hist_ps_elems) {
-                    if (d_hist_ps) MG_HIP(hipFree(d_hist_ps));
-                    d_hist_ps = nullptr;
-                    MG_HIP(hipMalloc(&d_hist_ps, need * sizeof(double)));
-                    hist_ps_elems = need;
-                }
-            }
-            MG_HIP(hipMemsetAsync(d_nonfinite, 0, sizeof(int), st));
-            MG_HIP(hipMemsetAsync(d_ps, 0, sizeof(double) * MGADMM_NMETRIC * Bp, st));
-            MG_HIP(hipMemsetAsync(d_cg_iters, 0, sizeof(int) * (size_t)max_it * 3 * Bp, st));
-            // Schedule of the outer loop (ADMM.py:546-646 is one loop with the stop test at its end):
-            //   SYNC     (MGADMM_LDS_ASYNC=0, or the CG coefficients are recorded: the host copies them out per iteration)
-            //            one stream, the host reads the metrics of an iteration and tests the stop criterion before it enqueues the next;
-            //   DEVSTOP  (check_stop) one stream, the stop test runs on the device (k_lds_stop_test sets the stop word, every
-            //            later launch returns at its guard), the host enqueues iterations ahead and looks at the word LAG
-            //            iterations late: same iterates and history, no host round trip per iteration;
-            //   CHUNKS   (fixed iteration count) one k_admm_lds launch runs a CHUNK of J iterations on every sample (the workgroup
-            //            keeps its sample: see the kernel); every iterate x_k goes to a buffer of its own, and the whole-batch
-            //            metric kernels of a chunk (delta_x_per_step re-reads x_k and x_{k+1} of the batch, 241 MB per iteration
-            //            at cfg2) run on a helper stream beside the launch of the next chunk, which leaves HBM idle.  Iterates
-            //            at chunk boundaries rotate through three buffers, the iterates inside a chunk and the per-sample metric
-            //            sums through two sets: launch c+2 overwrites what the metric kernels of chunk c read and waits for them.
-            //            J = 1 is the overlapped one-iteration-per-launch schedule of round 2.
-            enum { SYNC, DEVSTOP, CHUNKS };
-            // Per-sample stop (MGADMM_ADMM_PER_SAMPLE with check_stop): the test runs INSIDE k_admm_lds, after every iteration of a
-            // launch, on the sample the workgroup owns -- it needs nothing from outside the workgroup.  So the solve takes the
-            // CHUNKS schedule (SYNC when the CG coefficients are recorded): a sample that stops writes x_out[b] itself and sets
-            // its stop word, its workgroup returns at the guard of every later launch; the host reads the number of stopped
-            // samples LAG launches late and ends when it equals B.  The per-sample sums of every iteration go to a buffer of their
-            // own (no ring, no helper stream); delta_x_per_step is not formed; the whole-batch history is made at the end from the
-            // sums and the stop words (k_lds_ps_history).
-            const bool ps_mode = p.admm_convergence == MGADMM_ADMM_PER_SAMPLE && p.check_stop;
-            const int sched = (!lds_async || record) ? SYNC : ((p.check_stop && !ps_mode) ? DEVSTOP : CHUNKS);
-            if (ps_mode) {
-                const size_t need = (size_t)max_it * MGADMM_NMETRIC * Bp;
-                if (need > ps_full_elems) {
-                    if (d_ps_full) MG_HIP(hipFree(d_ps_full));
-                    d_ps_full = nullptr;
-                    ps_full_elems = 0;
-                    MG_HIP(hipMalloc(&d_ps_full, need * sizeof(double)));
-                    ps_full_elems = need;
-                }
-                MG_HIP(hipMemsetAsync(d_pstop, 0, sizeof(int) * ((size_t)Bp_max + 1), st));
-            }
+            LdsRun r;
+            r.B = B; r.Bp = (B + 63) / 64 * 64;
+            r.has_phi = p.ablation == MGADMM_ABL_NONE || p.ablation == MGADMM_ABL_DGLR;
+            r.has_zd = p.ablation != MGADMM_ABL_DGLR;
+            r.record = p.record_cg_coeffs && hist && hist->cg_alpha && hist->cg_beta;
+            r.cold = !state_in;
+            r.hist = hist;
             // The caller's output buffers ARE the working state of this path (same (B, T*N) layout): no copy-out at the end
             // (round 2 until here: seven 120 MB device copies per solve at cfg2 = 0.7 ms of a 59 ms solve).  The iterates are
             // assigned to buffers so that the one of the LAST iteration lands in x_out (an early stop on another buffer
             // costs one copy).  Outputs must not alias y / mask (mgadmm.h).
-            float* const xo_ = static_cast<float*>(x_out);
-            // buffers for the iterates: the workspace vectors this path does not use otherwise
-            static const int ring_ids[] = {V_XA, V_XB, V_ZUB, V_ZDB, V_PHIB, V_Y, V_MASK, V_R, V_P, V_Q, V_AP, V_RHS, V_TMP, V_IO0, V_IO1};
-            constexpr int NRING = (int)(sizeof(ring_ids) / sizeof(ring_ids[0]));
-            const int J = sched == CHUNKS ? std::max(1, std::min(std::min(lds_chunk, LDS_MAXJ_POOL), max_it)) : 1;
-            {   // buffers beyond the workspace vectors for chunks longer than 4 iterations (kept for the solver's lifetime)
-                const int need = LDS_SETS * (J - 1) + LDS_NBOUND - NRING;
-                while ((int)lds_ring_extra.size() < need) {
-                    float* b = nullptr;
-                    MG_HIP(hipMalloc(&b, vec_elems * sizeof(S)));
-                    lds_ring_extra.push_back(b);
-                    ws_bytes += (int64_t)(vec_elems * sizeof(S));
-                }
+            r.xo = static_cast<float*>(x_out);
+            r.s = ldssched::Schedule::pick(lds_async != 0, r.record, p.check_stop != 0, p.admm_convergence == MGADMM_ADMM_PER_SAMPLE,
+                                           lds_chunk, p.max_admm_iter);
+            const ldssched::Schedule& s = r.s;
+            const bool chunked = s.kind == ldssched::CHUNKS;
+            MG_TRY(ensure_hist_ps(hist, B));
+            MG_HIP(hipMemsetAsync(d_nonfinite, 0, sizeof(int), st));
+            MG_HIP(hipMemsetAsync(d_ps, 0, sizeof(double) * MGADMM_NMETRIC * r.Bp, st));
+            MG_HIP(hipMemsetAsync(d_cg_iters, 0, sizeof(int) * (size_t)s.max_it * 3 * r.Bp, st));
+            if (s.per_sample) {
+                MG_TRY(grow(d_ps_full, ps_full_elems, (size_t)s.max_it * MGADMM_NMETRIC * r.Bp));
+                MG_HIP(hipMemsetAsync(d_pstop, 0, sizeof(int) * ((size_t)Bp_max + 1), st));
             }
-            auto ring = [&](int j) -> float* { return j < NRING ? (float*)vec[ring_ids[j]] : lds_ring_extra[j - NRING]; };
-            // iterate k (k = 0: the initial guess) lives in xbuf(k)
-            auto xbuf = [&](int k) -> float* {
-                if (k == max_it) return xo_;
-                if (sched != CHUNKS) return ring(k & 1);
-                if (k % J == 0) return ring((k / J) % LDS_NBOUND);                                        // chunk boundary
-                return ring(LDS_NBOUND + ((k / J) % LDS_SETS) * (J - 1) + (k % J - 1));                    // inside chunk k / J
-            };
-            // zu, zd, phi and the dual variables: workspace vectors in the kernel's thread-major layout (lds_kernels.h,
-            // lds_state_index); a warm start is converted in, the exported state is converted out at the end
-            float *zu = vec[V_ZUA], *zd = vec[V_ZDA], *phi = vec[V_PHIA], *gam = vec[V_GAM], *gu = vec[V_GU], *gd = vec[V_GD];
-            if (state_in) {
-                const size_t nb = (size_t)B * TN * sizeof(float);
-                if (x0 != nullptr && xbuf(0) != x0) MG_HIP(hipMemcpyAsync(xbuf(0), x0, nb, hipMemcpyDeviceToDevice, st));
-                auto in = [&](float* dst, const void* src) {
-                    return src == nullptr ? (int)MGADMM_OK : mg_lds_state_layout(true, T, N, lds.TPG, B, (const float*)src, dst, lds_row_of_node(), st);
-                };
-                MG_TRY(in(zu, state_in->zu));
-                MG_TRY(in(gu, state_in->gamma_u));
-                MG_TRY(in(zd, state_in->zd));            // the vectors an ablation does not iterate on are carried through
-                MG_TRY(in(gd, state_in->gamma_d));
-                MG_TRY(in(phi, state_in->phi));
-                MG_TRY(in(gam, state_in->gamma));
-            } else {
-                float tm = 0, t2m = 0;
-                for (int t = 0; t < p.t_in; ++t) { tm += (float)t; t2m += (float)t * (float)t; }
-                tm /= (float)p.t_in;
-                t2m /= (float)p.t_in;
-                const float den = t2m - tm * tm;
-                MG_TRY(mg_lds_init(mask != nullptr, T, p.t_in, N, lds.TPG, B, tm, den, (const float*)y, (const float*)mask, xbuf(0), zu, zd, gam, gu, gd,
-                                   d_nonfinite, lds_row_of_node(), st));
+            MG_TRY(lds_ring_reserve(s.slots()));
+            lds_fill_args(r, y, mask);
+            MG_TRY(lds_state_in(r, x0, state_in));
+            if (s.kind == ldssched::DEVSTOP) {
+                r.a.stop = d_stop;
+                MG_HIP(hipMemsetAsync(d_stop, 0, sizeof(int), st));
             }
-            LdsArgs a{};
-            a.T = T; a.N = N; a.TN = (int)TN; a.TS = lds.TS; a.t_in = p.t_in; a.G = lds.G; a.B = B; a.Bp = Bp;
-            a.nthreads = lds.nthreads; a.NR = lds.NR; a.tail_pairs = lds.tail_pairs;
-            a.has_phi = has_phi; a.has_zd = has_zd;
-            const LhsDef dx = lhs_def(MGADMM_LHS_X);
-            a.lhsx_kind = dx.kind == 1 ? 1 : 0;
-            a.cx1 = (float)dx.c1; a.cx2 = (float)dx.c2;
-            a.band = g->mode == MGADMM_TEMPORAL_BAND; a.skip = g->skip;
-            a.q1 = a.band ? 0 : g->q1;
-            a.max_cg = p.max_cg_iter; a.record = record ? 1 : 0;
-            a.rho = (float)p.rho; a.rho_u = (float)p.rho_u; a.rho_d = (float)p.rho_d;
-            a.mu_u = (float)p.mu_u; a.mu_d1 = (float)p.mu_d1; a.mu_d2 = (float)p.mu_d2;
-            a.cg_tol2 = p.cg_tol * p.cg_tol;
-            a.csr = d_lds_csr; a.lds_img0 = lds.lds_img0; a.lds_img_ints = lds.lds_img_ints;
-            a.off_rp_u = lds.off_rp_u; a.off_rp_d = lds.off_rp_d;
-            a.off_en_u = lds.off_en_u; a.off_en_d = lds.off_en_d; a.off_lead_t = lds.off_lead_t; a.off_tail_t = lds.off_tail_t; a.off_diag = lds.off_diag;
-            a.npos = lds.npos_word; a.off_node = lds.off_node;
-            a.band_w = g->band_w;
-            a.zu = zu; a.zd = zd; a.phi = phi; a.gam = gam; a.gu = gu; a.gd = gd;
-            // staggered start (k_admm_lds): only when the launch runs several rounds of workgroups per CU
-            {
-                const int ncu = dev_cus > 0 ? dev_cus : 256;
-                int us = 48;
-                if (const char* e = getenv("MGADMM_LDS_STAGGER_US")) us = atoi(e);
-                a.stagger_wgs = ncu;
-                a.stagger_ticks = (B >= 2 * ncu && us > 0) ? us * 100 : 0;
+            if (chunked && !s.per_sample) MG_HIP(hipMemsetAsync(d_ps_ring, 0, sizeof(double) * LDS_SETS * s.J * MGADMM_NMETRIC * r.Bp, st));
+            if (s.per_sample) {
+                r.a.pstop = d_pstop; r.a.pstop_count = d_pstop + Bp_max; r.a.x_final = r.xo; r.a.admm_tol = p.admm_tol;
             }
-            a.y = (const float*)y; a.mask = (const float*)mask;
-            a.alpha_hist = record ? (float*)d_alpha_hist : nullptr; a.beta_hist = record ? (float*)d_beta_hist : nullptr;
-            a.nonfinite = d_nonfinite;
-            a.stop = sched == DEVSTOP ? d_stop : nullptr;
-            if (sched == DEVSTOP) MG_HIP(hipMemsetAsync(d_stop, 0, sizeof(int), st));
-            if (sched == CHUNKS && !ps_mode) MG_HIP(hipMemsetAsync(d_ps_ring, 0, sizeof(double) * LDS_SETS * J * MGADMM_NMETRIC * Bp, st));
-            int* const d_pcount = d_pstop + Bp_max;
-            if (ps_mode) {
-                a.pstop = d_pstop; a.pstop_count = d_pcount; a.x_final = xo_; a.admm_tol = p.admm_tol;
-            }
-            if (sp_B > 0) a.sp = d_sp;        // (B == sp_B: check_sample_params) the launches take the kernels k_admm_lds_pp
-            // number of stopped samples after launch `c`, read LAG launches late: true when every sample has stopped
-            auto all_stopped = [&](int c, bool* done) -> int {
-                MG_HIP(hipMemcpyAsync(h_flag + 1 + c % (LAG + 1), d_pcount, sizeof(int), hipMemcpyDeviceToHost, st));
-                MG_HIP(hipEventRecord(ev_ring[c % (LAG + 1)], st));
-                *done = false;
-                if (c >= LAG) {
-                    MG_HIP(hipEventSynchronize(ev_ring[(c - LAG) % (LAG + 1)]));
-                    *done = h_flag[1 + (c - LAG) % (LAG + 1)] == B;
-                }
-                return MGADMM_OK;
-            };
-            const size_t K = p.max_cg_iter;
-            int n_done = 0, rc_final = MGADMM_OK;
-            // the whole-batch metrics of iteration `it` (delta_x_per_step, norms / means over the samples) on stream `s`
-            auto batch_metrics = [&](int it, const double* ps, hipStream_t s) -> int {
-                MG_TRY(mg_lds_dxps(T, N, B, (const float*)xbuf(it + 1), (const float*)xbuf(it), d_m2, d_dxps + (size_t)it * T, a.stop, s));
-                hipLaunchKernelGGL(k_batch_metrics, dim3(MGADMM_NMETRIC), dim3(256), 0, s, ps, Bp, B,
-                                   d_hist + (size_t)it * MGADMM_NMETRIC,
-                                   (hist && hist->metrics_per_sample) ? d_hist_ps + (size_t)it * MGADMM_NMETRIC * B : nullptr);
-                MG_HIP(hipGetLastError());
-                return MGADMM_OK;
-            };
-            if (sched == CHUNKS) {
-                int c = 0;
-                for (int it0 = 0; it0 < max_it; it0 += J, ++c) {
-                    const int Jc = std::min(J, max_it - it0);
-                    a.first = it0 == 0 && !state_in;      // phi = Ldr x0 is formed by the first iteration of a cold start
-                    a.J = Jc;
-                    for (int k = 0; k <= Jc; ++k) a.xs[k] = xbuf(it0 + k);
-                    a.cg_iters = d_cg_iters + (size_t)it0 * 3 * Bp;
-                    a.ps = d_ps_ring + (size_t)(c % LDS_SETS) * J * MGADMM_NMETRIC * Bp;
-                    if (ps_mode) {
-                        a.ps = d_ps_full + (size_t)it0 * MGADMM_NMETRIC * Bp;
-                        a.it0 = it0;
-                        MG_TRY(launch_lds(a, B));
-                        n_done = it0 + Jc;
-                        bool done = false;
-                        MG_TRY(all_stopped(c, &done));
-                        if (done) break;          // the launches enqueued since returned at their guards
-                        continue;
-                    }
-                    // launch c overwrites the iterate buffers and the metric sums that the metric kernels of chunk c-3 read (interior
-                    // set and metric set c % 3; boundary buffer (c + 1) % 4 = the start of chunk c-3).  Two sets / three boundary
-                    // buffers (until the end of round 3) made launch c wait for the metrics of chunk c-2, which run BESIDE launch c-1
-                    // and get CU slots only when it drains: 0.45 ms between two 26 ms launches (profiles/r03/cfg2_iteration_timeline.txt)
-                    if (c >= LDS_SETS) MG_HIP(hipStreamWaitEvent(st, ev_side[(c - LDS_SETS) % LDS_NBOUND], 0));
-                    MG_TRY(launch_lds(a, B));
-                    MG_HIP(hipEventRecord(ev_main[c % LDS_NBOUND], st));
-                    MG_HIP(hipStreamWaitEvent(st_side, ev_main[c % LDS_NBOUND], 0));
-                    for (int k = 0; k < Jc; ++k) MG_TRY(batch_metrics(it0 + k, a.ps + (size_t)k * MGADMM_NMETRIC * Bp, st_side));
-                    MG_HIP(hipEventRecord(ev_side[c % LDS_NBOUND], st_side));
-                    n_done = it0 + Jc;
-                }
-                if (c > 0 && !ps_mode)            // join the helper stream (its kernels run in order: the last event covers all)
-                    MG_HIP(hipStreamWaitEvent(st, ev_side[(c - 1) % LDS_NBOUND], 0));
-            }
-            for (int it = 0; sched != CHUNKS && it < max_it; ++it) {
-                a.first = it == 0 && !state_in;      // phi = Ldr x0 is formed by the first launch of a cold start
-                a.J = 1;
-                a.xs[0] = xbuf(it); a.xs[1] = xbuf(it + 1);
-                a.cg_iters = d_cg_iters + (size_t)it * 3 * Bp;
-                a.ps = d_ps;
-                if (ps_mode) { a.ps = d_ps_full + (size_t)it * MGADMM_NMETRIC * Bp; a.it0 = it; }
-                if (record) {
-                    MG_TRY(fill((S*)d_alpha_hist, 3 * K * Bp, (S)NAN));
-                    MG_TRY(fill((S*)d_beta_hist, 3 * K * Bp, (S)NAN));
-                }
-                MG_TRY(launch_lds(a, B));
-                if (!ps_mode) MG_TRY(batch_metrics(it, a.ps, st));
-                if (record) {
-                    for (int w = 0; w < 3; ++w) {
-                        if (w == 2 && !has_zd) continue;
-                        double* ao = hist->cg_alpha + ((size_t)it * 3 + w) * K * B;
-                        double* bo = hist->cg_beta + ((size_t)it * 3 + w) * K * B;
-                        MG_TRY(fetch_hist(d_alpha_hist + (size_t)w * K * Bp, K * Bp, ao, B, Bp, K));
-                        MG_TRY(fetch_hist(d_beta_hist + (size_t)w * K * Bp, K * Bp, bo, B, Bp, K));
-                    }
-                }
-                n_done = it + 1;
-                if (ps_mode) {            // (the host is in step with the device here: the count of this very launch)
-                    MG_HIP(hipMemcpyAsync(h_flag + 1, d_pcount, sizeof(int), hipMemcpyDeviceToHost, st));
-                    MG_HIP(hipStreamSynchronize(st));
-                    if (h_flag[1] == B) break;
-                } else if (sched == DEVSTOP) {
-                    MG_TRY(mg_lds_stop_test(d_hist + (size_t)it * MGADMM_NMETRIC, d_nonfinite, has_phi, has_zd, p.admm_tol, it, d_stop, st));
-                    MG_HIP(hipMemcpyAsync(h_flag + 1 + it % (LAG + 1), d_stop, sizeof(int), hipMemcpyDeviceToHost, st));
-                    MG_HIP(hipEventRecord(ev_ring[it % (LAG + 1)], st));
-                    if (it >= LAG) {
-                        MG_HIP(hipEventSynchronize(ev_ring[(it - LAG) % (LAG + 1)]));
-                        if (h_flag[1 + (it - LAG) % (LAG + 1)] != 0) break;      // the launches enqueued since returned at their guards
-                    }
-                } else if (p.check_stop) {
-                    MG_HIP(hipMemcpyAsync(h_row, d_hist + (size_t)it * MGADMM_NMETRIC, sizeof(double) * MGADMM_NMETRIC,
-                                          hipMemcpyDeviceToHost, st));
-                    MG_HIP(hipMemcpyAsync(h_flag, d_nonfinite, sizeof(int), hipMemcpyDeviceToHost, st));
-                    MG_HIP(hipStreamSynchronize(st));
-                    bool finite = h_flag[0] == 0;
-                    for (int k = 0; k < MGADMM_NMETRIC; ++k) finite = finite && std::isfinite(h_row[k]);
-                    if (!finite) { rc_final = MGADMM_ERR_NONFINITE; break; }
-                    double pri = h_row[MGADMM_M_PRI_ZU], dual = h_row[MGADMM_M_DUAL_ZU];
-                    if (has_phi) { pri = std::max(pri, h_row[MGADMM_M_PRI_PHI]); dual = std::max(dual, h_row[MGADMM_M_DUAL_PHI]); }
-                    if (has_zd) { pri = std::max(pri, h_row[MGADMM_M_PRI_ZD]); dual = std::max(dual, h_row[MGADMM_M_DUAL_ZD]); }
-                    if (pri < p.admm_tol && dual < p.admm_tol) break;
-                }
-            }
-            if (sched == DEVSTOP) {
-                // the stop word after everything enqueued has run: 0 = no stop (all enqueued iterations ran), k > 0 = the stop
-                // test passed at the end of iteration k - 1, k < 0 = iteration -k - 1 met a NaN / Inf
-                MG_HIP(hipMemcpyAsync(h_flag + 1, d_stop, sizeof(int), hipMemcpyDeviceToHost, st));
-                MG_HIP(hipStreamSynchronize(st));
-                const int sw = h_flag[1];
-                if (sw > 0) n_done = sw;
-                else if (sw < 0) { n_done = -sw; rc_final = MGADMM_ERR_NONFINITE; }
-            }
+            if (sp_B > 0) r.a.sp = d_sp;      // (B == sp_B: check_sample_params) the launches take the kernels k_admm_lds_pp
+            MG_TRY(chunked ? lds_run_chunks(r) : lds_run_steps(r));
             std::vector<int> nps;         // per-sample stop: iterations of every sample
-            if (ps_mode) {
-                // n_done iterations were enqueued; the history from the stop words and the per-sample sums
-                int* const d_nps = d_pstop + Bp_max + 1;
-                MG_TRY(mg_lds_ps_history(d_ps_full, d_pstop, n_done, max_it, B, Bp, d_nps, d_hist,
-                                         (hist && hist->metrics_per_sample) ? d_hist_ps : nullptr, st));
-                nps.resize(B);
-                MG_HIP(hipMemcpyAsync(nps.data(), d_nps, sizeof(int) * B, hipMemcpyDeviceToHost, st));
-                MG_HIP(hipStreamSynchronize(st));
-                n_done = *std::max_element(nps.begin(), nps.end());
-            }
-            // (per-sample stop: a stopped sample stored x_out[b] itself, the others ran max_it iterations and xbuf(max_it) = x_out)
-            float* const xc = ps_mode ? xo_ : xbuf(n_done);
-            if (xc != xo_)        // early stop on the other parity
-                MG_HIP(hipMemcpyAsync(x_out, xc, (size_t)B * TN * sizeof(float), hipMemcpyDeviceToDevice, st));
-            if (state_out) {      // the state the caller asked for, in the reference's layout
-                auto out = [&](void* dst, const float* src) {
-                    return dst == nullptr ? (int)MGADMM_OK : mg_lds_state_layout(false, T, N, lds.TPG, B, src, (float*)dst, lds_row_of_node(), st);
-                };
-                MG_TRY(out(state_out->zu, zu));
-                MG_TRY(out(state_out->zd, zd));
-                if (has_phi) {
-                    MG_TRY(out(state_out->phi, phi));
-                    MG_TRY(out(state_out->gamma, gam));
-                }
-                MG_TRY(out(state_out->gamma_u, gu));
-                MG_TRY(out(state_out->gamma_d, gd));
-            }
-            return finish_history(hist, n_done, B, Bp, rc_final, ps_mode ? nps.data() : nullptr);
+            if (s.per_sample) MG_TRY(lds_finish_per_sample(r, nps));
+            // (per-sample stop: a stopped sample stored x_out[b] itself, the others ran max_it iterations and their last iterate is x_out)
+            float* const xc = s.per_sample ? r.xo : lds_xbuf(r, r.n_done);
+            if (xc != r.xo)       // early stop on another buffer
+                MG_HIP(hipMemcpyAsync(x_out, xc, (size_t)B * T * N * sizeof(float), hipMemcpyDeviceToDevice, st));
+            if (state_out) MG_TRY(lds_state_out(r, state_out));
+            return finish_history(hist, r.n_done, B, r.Bp, r.rc, s.per_sample ? nps.data() : nullptr);
         }
     }
 

@@ -1,8 +1,8 @@
-"""The three schedules of the LDS path's ADMM outer loop (csrc/engine.h, solve_lds) give the same bits.
+"""The three schedules of the LDS path's ADMM outer loop (csrc/lds_schedule.h; csrc/engine.h, solve_lds) give the same bits.
 
 SYNC (MGADMM_LDS_ASYNC=0): one stream, the host tests the stop criterion (ADMM.py:645-646) after every iteration.
 DEVSTOP (check_stop): the stop test runs on the device, later launches return at their guard, the host looks late.
-CHUNKS (fixed iteration count): one k_admm_lds launch runs J iterations on every sample (MGADMM_LDS_CHUNK, default 7; the
+CHUNKS (fixed iteration count): one k_admm_lds launch runs J iterations on every sample (MGADMM_LDS_CHUNK, default 16; the
 workgroup keeps its sample), every iterate goes to a buffer of its own and the whole-batch metric kernels of a chunk run on a
 helper stream beside the launch of the next chunk.
 Compared: x, the exported state, every history list and the iteration count -- bit for bit -- plus the stop iteration against
@@ -85,7 +85,7 @@ def test_fixed_iteration_count_overlapped_equals_synchronous(abl, task, B):
 
 @pytest.mark.parametrize("abl,task,B", [("None", "pred", 3), ("None", "pred", 300), ("DGLR", "mask", 70), ("DGTV", "pred", 130)])
 def test_several_iterations_per_launch_equal_one_per_launch(abl, task, B):
-    """Chunks of J iterations per launch (the workgroup keeps its sample, iterates in a ring of 2 (J - 1) + 3 buffers) against the
+    """Chunks of J iterations per launch (the workgroup keeps its sample, iterates in a ring of 3 (J - 1) + 4 buffers) against the
     synchronous one-iteration-per-launch loop: iteration counts that are a multiple of J, leave a remainder, fit one chunk,
     and need more chunks than there are buffer sets."""
     meta = load_golden("g4_meta.npz")
