@@ -114,6 +114,21 @@ def main():
     for i, a in enumerate(grid["mu_u"]):
         print(f"  {a:>13.3g} " + "".join(f"{mae[i * 3 + j]:>9.3f}" for j in range(3)))
 
+    # the other knob of the notebooks is the graph itself: 3 values of u_sigma x 3 of mu_u, again ONE batch -- every distinct
+    # sigma gets its own weight tables on the instance's neighbour lists, every sample reads the tables of its cell
+    grid = {"u_sigma": [25.0, 50.0, 100.0], "mu_u": [0.5 * admm_info["mu_u"], admm_info["mu_u"], 2 * admm_info["mu_u"]]}
+    blk._reset_history()
+    blk.admm_convergence = "per_sample"
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    xs, n_it, sets = blk.sweep(y[:nw], grid)
+    torch.cuda.synchronize(); dt = time.perf_counter() - t0
+    blk.admm_convergence = "whole_batch"
+    mae = [(ds.recover_data(xs[p][:, 12:]) - truth).abs().mean().item() for p in range(len(sets))]
+    print(f"sigma sweep: {len(sets)} cells x {nw} windows x {int(n_it.max())} ADMM iterations in {dt * 1e3:.1f} ms; MAE of the 12 predicted steps")
+    print("  u_sigma \\ mu_u " + "".join(f"{v:>9.3g}" for v in grid["mu_u"]))
+    for i, a in enumerate(grid["u_sigma"]):
+        print(f"  {a:>14.3g} " + "".join(f"{mae[i * 3 + j]:>9.3f}" for j in range(3)))
+
     ix, iy, mask = ds.get_interpolated_batch(starts, 0.4)
     blk._reset_history()
     x_int = blk.combined_loop(iy, mask=mask, print_info=False)

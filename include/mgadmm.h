@@ -157,7 +157,8 @@ typedef struct mgadmm_solver mgadmm_solver;
 /* "mgadmm <major>.<minor>.<patch> (gfx950)".  The minor number changes whenever a struct of this header grows (0.2:
  * mgadmm_params gained cg_convergence and max_inner_iter; 0.3: mgadmm_params gained admm_convergence, mgadmm_history gained
  * n_iters_per_sample): a caller built against an older header must be rebuilt -- compare the string before passing structs.
- * The patch number counts additions that leave every struct alone (0.3.1: mgadmm_solver_set_sample_params). */
+ * The patch number counts additions that leave every struct alone (0.3.1: mgadmm_solver_set_sample_params;
+ * 0.3.2: mgadmm_solver_set_sample_graphs). */
 const char* mgadmm_version(void);
 const char* mgadmm_last_error(void);
 
@@ -195,6 +196,28 @@ typedef struct {
  * mgadmm_two_loops and the fine-grained entry points (mgadmm_lhs, mgadmm_cg, mgadmm_phi_direct, mgadmm_apply) keep using
  * the scalars of mgadmm_params. */
 int mgadmm_solver_set_sample_params(mgadmm_solver* s, const mgadmm_sample_params* sp, int32_t B);
+/* Per-sample graph weights: sample b of the following mgadmm_solve / mgadmm_solve_from calls with this B reads W_u, W_d and
+ * W_d^T of graphs[set_of_sample[b]] (a sweep over u_sigma / d_sigma on W windows as one batch, each sample equal to the solve
+ * by a solver created on its own graph, bit for bit).  `graphs`: n_sets handles of mgadmm_graph_create that share the
+ * TOPOLOGY of the solver's graph -- the same neighbour lists in the same order; only the weights differ.  The tables are
+ * copied: the handles may be destroyed after the call.  set_of_sample: host int32[B].  n_sets == 0 clears the table.
+ * Synchronous (it waits for the device before the old table is freed).
+ *   - a null handle, B outside [1, max_batch], an index outside [0, n_sets), or a graph whose n_nodes, T, temporal_mode,
+ *     transpose_by_gather, q1_identity_t0, skip, reorder or internal node order differ from the solver's graph
+ *     -> MGADMM_ERR_INVALID;
+ *   - a set whose plan on the LDS-resident path differs from the solver's in anything but weights (an entry that is missing
+ *     because its weight underflowed to 0 and the caller's table builder dropped it, another k, other neighbour lists)
+ *     -> MGADMM_ERR_UNSUPPORTED; the message names the set and the first field that differs;
+ *   - MGADMM_F64, a band graph (MGADMM_TEMPORAL_BAND) or a graph the LDS path cannot hold -> MGADMM_ERR_UNSUPPORTED.
+ * While a table is set (decided when a solve starts, before anything runs) the refusals of mgadmm_solver_set_sample_params
+ * hold: another B -> MGADMM_ERR_INVALID; MGADMM_PATH_STREAM, MGADMM_CG_BATCH_MAX, or check_stop = 1 with
+ * MGADMM_ADMM_WHOLE_BATCH -> MGADMM_ERR_UNSUPPORTED (the messages contain "sample_graphs").  The launches take the kernels
+ * k_admm_lds_pp (MGADMM_Q_LDS_UNIT = 2); together with a weights table a sample has its own graph and its own six weights.
+ * History, resume (mgadmm_solve_from) and the per-sample stop work as without a table.  mgadmm_two_loops and the
+ * fine-grained entry points (mgadmm_lhs, mgadmm_cg, mgadmm_phi_direct, mgadmm_apply) IGNORE the table: they keep using the
+ * solver's own graph. */
+int mgadmm_solver_set_sample_graphs(mgadmm_solver* s, int32_t n_sets, mgadmm_graph* const* graphs, const int32_t* set_of_sample,
+                                    int32_t B);
 /* bytes of device workspace held by the solver */
 int64_t mgadmm_solver_workspace_bytes(const mgadmm_solver* s);
 /* which path (MGADMM_PATH_STREAM / MGADMM_PATH_LDS) a batch of size B would take */

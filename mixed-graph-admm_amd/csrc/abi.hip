@@ -51,6 +51,11 @@ int mgadmm_solver_set_sample_params(mgadmm_solver* s, const mgadmm_sample_params
     return s->eng->set_sample_params(sp, B);
 }
 
+int mgadmm_solver_set_sample_graphs(mgadmm_solver* s, int32_t n_sets, mgadmm_graph* const* graphs, const int32_t* set_of_sample, int32_t B) {
+    MG_REQUIRE(s, "set_sample_graphs: null solver");
+    return s->eng->set_sample_graphs(n_sets, graphs, set_of_sample, B);
+}
+
 int64_t mgadmm_solver_workspace_bytes(const mgadmm_solver* s) { return s ? s->eng->workspace_bytes() : 0; }
 int mgadmm_solver_path(const mgadmm_solver* s, int32_t B) { return s ? s->eng->path_for(B) : MGADMM_ERR_INVALID; }
 

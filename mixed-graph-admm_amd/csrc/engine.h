@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <thread>
 #include <type_traits>
 
 #include "common.h"
@@ -15,6 +16,7 @@
 #include "stream_kernels.h"
 #include "lds_args.h"
 #include "lds_plan.h"
+#include "lds_graph_sets.h"
 #include "lds_schedule.h"
 
 namespace {
@@ -99,6 +101,13 @@ struct Engine : EngineBase {
     int sp_B = 0;                 // samples of the table; 0 = none set
     std::vector<double> sp_val[6];   // rho, rho_u, rho_d, mu_u, mu_d1, mu_d2
     LdsSampleParams* d_sp = nullptr;   // [Bmax]
+    // per-sample graph weights (mgadmm_solver_set_sample_graphs, lds_graph_sets.h): the images of the sets back to back and the
+    // set of every sample; the solver's own image and the planner's switches are kept for the comparison with every set
+    int sg_B = 0, sg_sets = 0;    // samples / sets of the table; sg_B = 0: none set
+    int* d_sg_img = nullptr;      // [sg_sets][img_stride]
+    int* d_sg_set = nullptr;      // [Bp_max]
+    std::vector<int> lds_img_host;
+    ldsplan::Switches lds_sw;
     // iterate buffers of solve_lds by slot number (lds_schedule.h): the 15 workspace vectors this path does not use otherwise
     // hold the LDS_SETS (J - 1) + LDS_NBOUND = 13 slots of J = 4; chunks longer than 4 iterations (up to LDS_MAXJ) get the
     // rest in lds_ring_extra on the first solve that asks for them, kept for the solver's lifetime
@@ -132,7 +141,7 @@ struct Engine : EngineBase {
         fr(vec_pool); fr(partials); fr(d_rr); fr(d_alpha); fr(d_beta); fr(d_alpha_hist); fr(d_beta_hist);
         fr(d_active); fr(d_iters_tmp); fr(d_nact); fr(d_nonfinite); fr(d_ps); fr(d_hist); fr(d_dxps);
         fr(d_dxpart); fr(d_hist_ps); fr(d_cg_iters); fr(d_lds_csr); fr(d_m2); fr(d_stop); fr(d_ps_ring); fr(d_pstop); fr(d_ps_full);
-        fr(d_sp);
+        fr(d_sp); fr(d_sg_img); fr(d_sg_set);
         for (float* b : lds_ring_extra) if (b) (void)hipFree(b);
         if (st_side) (void)hipStreamDestroy(st_side);
         for (auto& e : ev_main) if (e) (void)hipEventDestroy(e);
@@ -570,10 +579,12 @@ struct Engine : EngineBase {
     }
 
     // record b of the device table from sample b's six doubles: the expressions and casts solve_lds uses for the scalars
-    int upload_sample_params() {
-        std::vector<LdsSampleParams> rec((size_t)sp_B);
+    // (n records; without a weights table -- a solve with a graph table alone -- every record holds the scalars)
+    int upload_sample_params() { return upload_sample_params(sp_B); }
+    int upload_sample_params(int n) {
+        std::vector<LdsSampleParams> rec((size_t)n);
         const double scalar[6] = {p.rho, p.rho_u, p.rho_d, p.mu_u, p.mu_d1, p.mu_d2};
-        for (int b = 0; b < sp_B; ++b) {
+        for (int b = 0; b < n; ++b) {
             double w[6];
             for (int f = 0; f < 6; ++f) w[f] = sp_val[f].empty() ? scalar[f] : sp_val[f][(size_t)b];
             const LhsDef dx = lhs_def_of(MGADMM_LHS_X, p.ablation, w[0], w[1], w[2], w[3], w[5]);
@@ -602,6 +613,95 @@ struct Engine : EngineBase {
         }
         if (p.check_stop && p.admm_convergence == MGADMM_ADMM_WHOLE_BATCH) {
             mg_set_error("solve: sample_params with check_stop need admm_convergence per_sample (the whole_batch stop test would sum "
+                         "the residuals of different problems); or run a fixed count with check_stop = 0");
+            return MGADMM_ERR_UNSUPPORTED;
+        }
+        return MGADMM_OK;
+    }
+
+    // ---------------------------------------------------------------- per-sample graph weights
+    // Sample b reads the weights of set set_of_sample[b]; every set shares the solver's topology (lds_graph_sets.h plans each
+    // set with the solver's switches and names the first difference).  Synchronous: the old table is freed after the device
+    // has finished whatever read it.  mgadmm_two_loops and the fine-grained entry points keep using the solver's own graph.
+    int set_sample_graphs(int n_sets, mgadmm_graph* const* graphs, const int32_t* set_of_sample, int B) override {
+        MG_HIP(hipSetDevice(g->device));
+        if (n_sets == 0) {
+            if (d_sg_img) {
+                MG_HIP(hipDeviceSynchronize());
+                (void)hipFree(d_sg_img);
+                d_sg_img = nullptr;
+            }
+            sg_B = sg_sets = 0;
+            return MGADMM_OK;
+        }
+        MG_REQUIRE(n_sets >= 1 && graphs && set_of_sample, "set_sample_graphs: n_sets %d needs graphs and set_of_sample", n_sets);
+        MG_REQUIRE(B >= 1 && B <= Bmax, "set_sample_graphs: batch %d outside [1, max_batch=%d]", B, Bmax);
+        for (int b = 0; b < B; ++b)
+            MG_REQUIRE(set_of_sample[b] >= 0 && set_of_sample[b] < n_sets, "set_sample_graphs: set_of_sample[%d] = %d outside [0, n_sets=%d)",
+                       b, set_of_sample[b], n_sets);
+        for (int s = 0; s < n_sets; ++s) {
+            const mgadmm_graph* q = graphs[s];
+            MG_REQUIRE(q, "set_sample_graphs: graphs[%d] is null", s);
+            MG_REQUIRE(q->N == N && q->T == T, "set_sample_graphs: graphs[%d] has N = %d, T = %d, the solver's graph N = %d, T = %d", s, q->N, q->T, N, T);
+            MG_REQUIRE(q->device == g->device, "set_sample_graphs: graphs[%d] lives on device %d, the solver on %d", s, q->device, g->device);
+            MG_REQUIRE(q->mode == g->mode && q->transpose_by_gather == g->transpose_by_gather && q->q1 == g->q1 && q->skip == g->skip,
+                       "set_sample_graphs: graphs[%d] differs from the solver's graph in temporal_mode, transpose_by_gather, q1_identity_t0 or skip", s);
+            MG_REQUIRE(q->reorder == g->reorder && q->has_perm == g->has_perm && q->perm == g->perm,
+                       "set_sample_graphs: graphs[%d] has another internal node order than the solver's graph", s);
+        }
+        const char* why = nullptr;
+        if (!std::is_same<S, float>::value) why = "float64 arithmetic runs on the streaming path";
+        else if (!lds.ok) why = "the LDS-resident path cannot hold this graph (it needs T*N*8 B + tables <= 160 KiB and N*G <= 1024)";
+        else if (g->mode == MGADMM_TEMPORAL_BAND) why = "a band graph (line graph) has no W_d tables to vary";
+        if (why) {
+            mg_set_error("set_sample_graphs: sample_graphs (per-sample graph weights) are implemented by the LDS-resident float32 path only: %s", why);
+            return MGADMM_ERR_UNSUPPORTED;
+        }
+        // plan every set (the bank search of a set takes as long as the solver's own: sets are planned side by side)
+        std::vector<ldsplan::Input> sets;
+        for (int s = 0; s < n_sets; ++s)
+            sets.push_back(ldsplan::Input{T, N, false, graphs[s]->transpose_by_gather != 0, graphs[s]->hWu, graphs[s]->hWd, graphs[s]->hWdT});
+        std::vector<int> table;
+        std::string differs;
+        int bad = -1;
+        if (!ldssets::build_table(lds, lds_img_host, sets, lds_sw, table, &bad, differs, std::min(8, (int)std::thread::hardware_concurrency()))) {
+            mg_set_error("set_sample_graphs: sample_graphs set %d does not share the solver's topology -- %s (a weight that underflowed to 0 and "
+                         "was dropped, another k or other neighbour lists?)", bad, differs.c_str());
+            return MGADMM_ERR_UNSUPPORTED;
+        }
+        std::vector<int> set_of((size_t)Bp_max, 0);
+        std::copy(set_of_sample, set_of_sample + B, set_of.begin());
+        int* fresh = nullptr;
+        MG_HIP(hipMalloc(&fresh, sizeof(int) * table.size()));
+        if (hipMemcpy(fresh, table.data(), sizeof(int) * table.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(fresh);
+            mg_set_error("set_sample_graphs: upload of the images failed");
+            return MGADMM_ERR_HIP;
+        }
+        if (!d_sg_set) MG_HIP(hipMalloc(&d_sg_set, sizeof(int) * (size_t)Bp_max));
+        MG_HIP(hipDeviceSynchronize());          // no launch reads the old table any more
+        MG_HIP(hipMemcpy(d_sg_set, set_of.data(), sizeof(int) * set_of.size(), hipMemcpyHostToDevice));
+        if (d_sg_img) (void)hipFree(d_sg_img);
+        d_sg_img = fresh;
+        sg_B = B; sg_sets = n_sets;
+        return MGADMM_OK;
+    }
+
+    // A solve with a graph table set: the refusals of check_sample_params, before anything is enqueued
+    int check_sample_graphs(int B) const {
+        MG_REQUIRE(B == sg_B, "solve: the sample_graphs table holds %d samples, the solve has B = %d", sg_B, B);
+        const char* why = nullptr;
+        if (!std::is_same<S, float>::value) why = "float64 arithmetic runs on the streaming path";
+        else if (p.path == MGADMM_PATH_STREAM) why = "path is MGADMM_PATH_STREAM";
+        else if (p.cg_convergence == MGADMM_CG_BATCH_MAX) why = "cg_convergence batch_max runs on the streaming path";
+        else if (!lds.ok) why = "the LDS-resident path cannot hold this graph (it needs T*N*8 B + tables <= 160 KiB and N*G <= 1024)";
+        else if (g->mode == MGADMM_TEMPORAL_BAND) why = "a band graph (line graph) has no W_d tables to vary";
+        if (why) {
+            mg_set_error("solve: sample_graphs (per-sample graph weights) are implemented by the LDS-resident float32 path only: %s", why);
+            return MGADMM_ERR_UNSUPPORTED;
+        }
+        if (p.check_stop && p.admm_convergence == MGADMM_ADMM_WHOLE_BATCH) {
+            mg_set_error("solve: sample_graphs with check_stop need admm_convergence per_sample (the whole_batch stop test would sum "
                          "the residuals of different problems); or run a fixed count with check_stop = 0");
             return MGADMM_ERR_UNSUPPORTED;
         }
@@ -1221,6 +1321,7 @@ struct Engine : EngineBase {
         if (state_in) MG_TRY(check_state_in(x0, state_in));
         st = s;
         if (sp_B > 0) MG_TRY(check_sample_params(B));
+        if (sg_B > 0) MG_TRY(check_sample_graphs(B));
         if (p.path == MGADMM_PATH_LDS && !lds.ok) {
             mg_set_error("solve: the LDS-resident path needs float32, T*N*8 B + CSR <= 160 KiB and N*G <= 1024 (N=%d, T=%d)", N, T);
             return MGADMM_ERR_UNSUPPORTED;
@@ -1494,7 +1595,8 @@ struct Engine : EngineBase {
         // which k_admm_lds instance, its geometry and the image of its tables: plain host code, lds_plan.h
         std::vector<int> img;
         const ldsplan::Input in{T, N, g->mode == MGADMM_TEMPORAL_BAND, g->transpose_by_gather != 0, g->hWu, g->hWd, g->hWdT};
-        const ldsplan::Status planned = ldsplan::make(in, ldsplan::Switches::from_env(), lds, img);
+        lds_sw = ldsplan::Switches::from_env();
+        const ldsplan::Status planned = ldsplan::make(in, lds_sw, lds, img);
         if (planned == ldsplan::ROWS_DO_NOT_FIT) {
             mg_set_error("lds: row plan does not fit its launch word (%d waves)", lds.block / 64);
             return MGADMM_ERR_INVALID;
@@ -1502,6 +1604,7 @@ struct Engine : EngineBase {
         if (planned == ldsplan::NO_PLAN) return MGADMM_OK;
         MG_HIP(hipMalloc(&d_lds_csr, sizeof(int) * img.size()));
         MG_HIP(hipMemcpy(d_lds_csr, img.data(), sizeof(int) * img.size(), hipMemcpyHostToDevice));
+        lds_img_host = img;
         MG_HIP(hipMalloc(&d_m2, sizeof(double) * T * N * (1 + (size_t)(Bmax + 63) / 64)));
         MG_HIP(hipMalloc(&d_stop, sizeof(int)));
         MG_HIP(hipMemset(d_stop, 0, sizeof(int)));
@@ -1802,6 +1905,11 @@ struct Engine : EngineBase {
                 r.a.pstop = d_pstop; r.a.pstop_count = d_pstop + Bp_max; r.a.x_final = r.xo; r.a.admm_tol = p.admm_tol;
             }
             if (sp_B > 0) r.a.sp = d_sp;      // (B == sp_B: check_sample_params) the launches take the kernels k_admm_lds_pp
+            if (sg_B > 0) {                   // (B == sg_B: check_sample_graphs) workgroup b reads the image of set d_sg_set[b]
+                if (sp_B == 0) MG_TRY(upload_sample_params(B));      // no weights table: records of the scalars, the same kernels
+                r.a.sp = d_sp;
+                r.a.csr = d_sg_img; r.a.img_stride = ldssets::img_stride(lds); r.a.gset = d_sg_set;
+            }
             MG_TRY(chunked ? lds_run_chunks(r) : lds_run_steps(r));
             std::vector<int> nps;         // per-sample stop: iterations of every sample
             if (s.per_sample) MG_TRY(lds_finish_per_sample(r, nps));

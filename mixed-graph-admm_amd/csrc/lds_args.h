@@ -69,6 +69,11 @@ struct LdsArgs : LdsArgsCore {
     unsigned long long npos;     // 4-bit field w: positions of the W_d^T table (leading entries + tail) wave w gathers -- the largest
                                  // in-degree among its rows; the table width when the rows are in node order
     int off_node;                // offset in the global image of node_of_row[NR]: the node in HBM of LDS row r (ghost rows: 0)
+    // Per-sample graph weights (mgadmm_solver_set_sample_graphs; read by the kernels k_admm_lds_pp only; behind everything else):
+    // csr then holds the images of S weight sets of one topology, set s at csr + s * img_stride, and workgroup b reads the
+    // weights of set gset[b] (lds_graph_sets.h)
+    int img_stride;              // ints between two images
+    const int* gset;             // [Bp] device table, or nullptr: every workgroup reads set 0
 };
 
 // Execution plan of k_admm_lds chosen by ldsplan::make (lds_plan.h)

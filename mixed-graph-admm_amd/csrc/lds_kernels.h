@@ -872,6 +872,17 @@ __device__ __forceinline__ int lds_cg(LdsCtx<TPG, BAND, NU, ND, TP>& c, BlockRed
 #else
 #define MG_LDS_W(field) (a.sp[b].field)
 #endif
+// Per-sample graph weights (mgadmm_solver_set_sample_graphs): the images of S weight sets of one topology lie back to back
+// at a stride of LdsArgs::img_stride ints, workgroup b reads the one of set gset[b] (no table: set 0).  The base is formed
+// where it is used, from a workgroup-uniform load of the set number through the constant address space like MG_LDS_W: it
+// stays a scalar register pair, and every read of weights (the copy to LDS, the register rows, the diagonals) goes through
+// it.  node_of_row and the offsets in the entries are structure, equal in every set.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MG_LDS_IMG(args) ((args).csr + ((args).gset != nullptr ? (size_t)(unsigned)(args).img_stride * \
+                          (size_t)(unsigned)((const int __attribute__((address_space(4)))*)(args).gset)[b] : (size_t)0))
+#else
+#define MG_LDS_IMG(args) ((args).csr + ((args).gset != nullptr ? (size_t)(args).img_stride * (size_t)(args).gset[b] : (size_t)0))
+#endif
 #else
 #ifdef MGADMM_LDS_PER_SAMPLE_STOP
 #define MG_LDS_KERNEL k_admm_lds_ps
@@ -882,6 +893,7 @@ __device__ __forceinline__ int lds_cg(LdsCtx<TPG, BAND, NU, ND, TP>& c, BlockRed
 #endif
 #define MG_LDS_PSTOP_ON(args) true
 #define MG_LDS_W(field) (a.field)
+#define MG_LDS_IMG(args) (args).csr
 #endif
 template <int TPG, bool BAND, int MAXT, bool SB, int NU = 0, int ND = 0, bool SLOTS = false, int TP = -1>
 __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERNEL(LdsArgs a_in) {
@@ -917,7 +929,7 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
     }
     // graph image -> LDS once per launch, eight words per thread in flight
     {
-        const int* src = a_in.csr + a_in.lds_img0;
+        const int* src = MG_LDS_IMG(a_in) + a_in.lds_img0;
         const int nimg = a_in.lds_img_ints;
         for (int k0 = tid; k0 < nimg; k0 += 8 * nthr) {
             int wv[8];
@@ -1006,7 +1018,7 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
     for (int k = 0; k < TPG; ++k) { c.kN4[k] = 4u * (unsigned)k * (unsigned)a.N; MG_PIN_S(c.kN4[k]); }
     c.so0 = c.active ? 4u * TPG * (unsigned)tid : 0u;
     {
-        const int* tab = ENTG ? a.csr : img - a.lds_img0;          // where offsets into the image point
+        const int* tab = ENTG ? MG_LDS_IMG(a) : img - a.lds_img0;          // where offsets into the image point
         c.en_u = reinterpret_cast<const i2v*>(tab + a.off_en_u);
         c.en_d = reinterpret_cast<const i2v*>(tab + a.off_en_d);
         c.lead_t = reinterpret_cast<const i2v*>(tab + a.off_lead_t);
@@ -1014,7 +1026,7 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
     }
     c.wdiag = mk2(0.f, 0.f);
     if constexpr (!BAND) {
-        const float* dg = reinterpret_cast<const float*>(a.csr + a.off_diag);      // [NR] W_d diagonal, [NR] W_d^T diagonal
+        const float* dg = reinterpret_cast<const float*>(MG_LDS_IMG(a) + a.off_diag);      // [NR] W_d diagonal, [NR] W_d^T diagonal
         c.wdiag = mk2(dg[c.i], dg[a.NR + c.i]);
     }
     // the thread's rows of the fixed-width tables (uniform instances), requested ahead of the phase that precedes their use

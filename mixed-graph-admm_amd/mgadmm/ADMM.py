@@ -72,6 +72,31 @@ def _check_sample_params(sample_params, B):
     return out
 
 
+GRAPH_PARAM_NAMES = ("u_sigma", "d_sigma")
+
+
+def _check_graph_params(graph_params, B):
+    """``graph_params`` of ``solve``: dict with u_sigma and / or d_sigma -> 1-D sequence / tensor of length B, as a dict
+    name -> float64 array.  Raises ValueError for an unknown name, a wrong length, a value that is not finite or <= 0."""
+    if not hasattr(graph_params, "items"):
+        raise ValueError(f"graph_params must be a dict with keys out of {GRAPH_PARAM_NAMES}, got {type(graph_params).__name__}")
+    out = {}
+    for name, vals in graph_params.items():
+        if name not in GRAPH_PARAM_NAMES:
+            raise ValueError(f"graph_params: unknown key {name!r} (expected some of {GRAPH_PARAM_NAMES})")
+        v = vals.detach().cpu().numpy() if torch.is_tensor(vals) else np.asarray(vals)
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.ndim != 1 or v.shape[0] != B:
+            raise ValueError(f"graph_params[{name!r}] must be 1-D of length B = {B}, got shape {tuple(v.shape)}")
+        if not np.isfinite(v).all():
+            raise ValueError(f"graph_params[{name!r}][{int(np.nonzero(~np.isfinite(v))[0][0])}] is not finite")
+        bad = np.nonzero(v <= 0)[0]
+        if bad.size:
+            raise ValueError(f"graph_params[{name!r}][{int(bad[0])}] = {v[bad[0]]}: u_sigma and d_sigma must be > 0")
+        out[name] = v
+    return out
+
+
 class ADMM_algorithm():
     """MI355X-native mixed-graph ADMM solver with the reference's interface (ADMM.py:15).
 
@@ -138,15 +163,10 @@ class ADMM_algorithm():
 
         assert ablation in ['None', 'DGTV', 'DGLR', 'UT'], "ablation should be in ['None', 'DGTV', 'DGLR', 'UT']"
         self.ablation = ablation
-        self.u_ew = _g.undirected_graph_from_distance(self.connect_list, self.dist_list, u_sigma=u_sigma)
-        if expand_time_dim:
-            self.u_ew = _u.expand_time_dimension(self.u_ew, T)
-        if not use_line_graph:
-            self.d_ew = _g.directed_graph_from_distance(self.connect_list, self.dist_list, d_sigma=d_sigma)
-            if expand_time_dim:
-                self.d_ew = _u.expand_time_dimension(self.d_ew, T - 1)
-        else:
-            self.d_ew, self.time_list = _u.skip_connection_tables(self.n_nodes, T, skip_connection)
+        self.u_sigma, self.d_sigma, self.expand_time_dim = u_sigma, d_sigma, expand_time_dim
+        self.u_ew, self.d_ew, time_list = self._weight_tables(u_sigma, d_sigma)
+        if use_line_graph:
+            self.time_list = time_list
 
         self.rho, self.rho_u, self.rho_d = ADMM_info['rho'], ADMM_info['rho_u'], ADMM_info['rho_d']
         self.mu_u, self.mu_d1, self.mu_d2 = ADMM_info['mu_u'], ADMM_info['mu_d1'], ADMM_info['mu_d2']
@@ -168,6 +188,23 @@ class ADMM_algorithm():
         self._solvers = {}     # (C, dtype) -> [handle, Bmax]
         self._reset_history()
         self._set_res_name()
+
+    def _weight_tables(self, u_sigma, d_sigma):
+        """``(u_ew, d_ew, time_list)`` of this instance's mode for a pair of sigmas (None: the reference's default), from
+        ``connect_list`` and ``dist_list``: what the constructor stores, and what ``solve(graph_params=...)`` builds for
+        every distinct pair.  ``time_list`` is None unless the instance uses the line graph, whose d_ew has no sigma."""
+        _g, T = self._tables_mod, self.T
+        u_ew = _g.undirected_graph_from_distance(self.connect_list, self.dist_list, u_sigma=u_sigma)
+        if self.expand_time_dim:
+            u_ew = _u.expand_time_dimension(u_ew, T)
+        time_list = None
+        if not self.use_line_graph:
+            d_ew = _g.directed_graph_from_distance(self.connect_list, self.dist_list, d_sigma=d_sigma)
+            if self.expand_time_dim:
+                d_ew = _u.expand_time_dimension(d_ew, T - 1)
+        else:
+            d_ew, time_list = _u.skip_connection_tables(self.n_nodes, T, self.skip_connection)
+        return u_ew, d_ew, time_list
 
     # ------------------------------------------------------------------ bookkeeping
     def _set_res_name(self):
@@ -196,6 +233,7 @@ class ADMM_algorithm():
             self.d_ew, self.time_list = _u.skip_connection_tables(self.n_nodes, self.T, 1)
         else:
             self.use_line_graph = False
+            self.d_sigma = None
             self.d_ew = _u.expand_time_dimension(
                 self._tables_mod.directed_graph_from_distance(self.connect_list, self.dist_list, d_sigma=None), self.T - 1)
         assert ablation in ['None', 'DGTV', 'DGLR', 'UT']
@@ -250,7 +288,13 @@ class ADMM_algorithm():
             for k2 in [k2 for k2 in self._solvers if k2[0] == Cn]:
                 _lib.lib.mgadmm_solver_destroy(self._solvers.pop(k2)[0])
             ent[0].close()
-        u_ew = self._time_invariant(self.u_ew, "u_ew")
+        gph = self._make_graph(Cn, self.u_ew, self.d_ew)
+        self._graphs[Cn] = (gph, key)
+        return gph
+
+    def _make_graph(self, Cn, u_ew, d_ew):
+        """A device graph of this instance's topology, mode and node order with the weight tables ``u_ew`` / ``d_ew``."""
+        u_ew = self._time_invariant(u_ew, "u_ew")
         u_csr = expand_channels(tables_to_csr(self.connect_list, u_ew, 1), Cn)
         N = self.n_nodes * Cn
         reorder = self.reorder
@@ -261,15 +305,14 @@ class ADMM_algorithm():
         reorder = {'rcm': 1, 'cluster': 2}[reorder] if isinstance(reorder, str) else int(reorder)
         dev = self.device
         if self.use_line_graph:
-            bw = self.d_ew[:, :, 0].contiguous().cpu().numpy()
+            bw = d_ew[:, :, 0].contiguous().cpu().numpy()
             gph = Graph(N, self.T, u_csr, None, band_w=bw, skip=self.skip_connection, reorder=reorder,
                         device=dev.index or 0)
         else:
-            d_ew = self._time_invariant(self.d_ew, "d_ew")
+            d_ew = self._time_invariant(d_ew, "d_ew")
             d_csr = expand_channels(tables_to_csr(self.connect_list, d_ew, 0), Cn)
             gph = Graph(N, self.T, u_csr, d_csr, transpose_by_gather=not self.use_kNN,
                         q1_identity_t0=self.bug_compat, reorder=reorder, device=dev.index or 0)
-        self._graphs[Cn] = (gph, key)
         return gph
 
     def _params(self, dtype, B):
@@ -323,6 +366,71 @@ class ADMM_algorithm():
             yield
         finally:
             _lib.lib.mgadmm_solver_set_sample_params(h, None, 0)
+
+    def _check_graph_sets(self, graph_sets, graph_of_sample, graph_params, B):
+        """The graph arguments of ``solve`` as ``(sets, set_of_sample)`` -- a list of (u_ew, d_ew) tables and an int32 array of
+        length B -- or None without them.  ValueError for what can be refused before the library is touched."""
+        if graph_params is None and graph_sets is None:
+            if graph_of_sample is not None:
+                raise ValueError("graph_of_sample needs graph_sets")
+            return None
+        if graph_params is not None and graph_sets is not None:
+            raise ValueError("graph_params and graph_sets exclude each other (graph_params builds the sets itself)")
+        if self.use_line_graph:
+            raise ValueError("graph_params / graph_sets: a line-graph instance has no spatial W_d tables to vary (use_line_graph=True)")
+        if graph_params is not None:
+            gp = _check_graph_params(graph_params, B)
+            if getattr(self, "dist_list", None) is None:
+                raise ValueError("graph_params: the instance was built without distances (dist_list), its tables cannot be rebuilt")
+            cols = [gp[nm].tolist() if nm in gp else [getattr(self, nm)] * B for nm in GRAPH_PARAM_NAMES]
+            pairs, index = [], {}
+            gos = np.zeros(B, dtype=np.int32)
+            for b, pair in enumerate(zip(*cols)):
+                if pair not in index:
+                    index[pair] = len(pairs)
+                    pairs.append(pair)
+                gos[b] = index[pair]
+            return [self._weight_tables(us, ds)[:2] for us, ds in pairs], gos
+        sets = []
+        for j, pair in enumerate(graph_sets):
+            if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+                raise ValueError(f"graph_sets[{j}] must be a pair (u_ew, d_ew)")
+            u_ew, d_ew = (torch.as_tensor(t).float() for t in pair)
+            for nm, t, own in (("u_ew", u_ew, self.u_ew), ("d_ew", d_ew, self.d_ew)):
+                if tuple(t.shape) not in (tuple(own.shape), tuple(own.shape[-2:])):
+                    raise ValueError(f"graph_sets[{j}]: {nm} has shape {tuple(t.shape)}, the instance's has {tuple(own.shape)}")
+            sets.append((u_ew, d_ew))
+        if not sets:
+            raise ValueError("graph_sets is empty")
+        if graph_of_sample is None:
+            raise ValueError("graph_sets needs graph_of_sample (the set of every sample)")
+        gos = graph_of_sample.detach().cpu().numpy() if torch.is_tensor(graph_of_sample) else np.asarray(graph_of_sample)
+        if gos.ndim != 1 or gos.shape[0] != B or gos.dtype.kind not in "iu":
+            raise ValueError(f"graph_of_sample must be B = {B} integers, got shape {tuple(gos.shape)} of {gos.dtype}")
+        bad = np.nonzero((gos < 0) | (gos >= len(sets)))[0]
+        if bad.size:
+            raise ValueError(f"graph_of_sample[{int(bad[0])}] = {int(gos[bad[0]])} out of range for {len(sets)} graph sets")
+        return sets, np.ascontiguousarray(gos, dtype=np.int32)
+
+    @contextlib.contextmanager
+    def _graph_table(self, h, Cn, gs, B):
+        """Per-sample graph weights (``_check_graph_sets`` output) set on solver ``h`` for the solves inside the block: a device
+        graph per set, closed when the block ends, where the table is cleared as well."""
+        if gs is None:
+            yield
+            return
+        sets, gos = gs
+        graphs = []
+        try:
+            for u_ew, d_ew in sets:
+                graphs.append(self._make_graph(Cn, u_ew, d_ew))
+            handles = (C.c_void_p * len(graphs))(*[g.handle for g in graphs])
+            _lib.check(_lib.lib.mgadmm_solver_set_sample_graphs(h, len(graphs), handles, gos.ctypes.data_as(C.POINTER(C.c_int32)), B))
+            yield
+        finally:
+            _lib.lib.mgadmm_solver_set_sample_graphs(h, 0, None, None, 0)
+            for g in graphs:
+                g.close()
 
     def _dtype_for(self, t):
         if self.compute_dtype == 'match':
@@ -482,7 +590,7 @@ class ADMM_algorithm():
         return None
 
     def solve(self, y, mask=None, differential=False, print_info=False, return_state=True, per_sample_history=False,
-              warm_start=None, sample_params=None):
+              warm_start=None, sample_params=None, graph_sets=None, graph_of_sample=None, graph_params=None):
         """Run the ADMM loop and return ``(x, (zu, zd), phi, history)``; ``history`` is a dict with the
         same lists that are also stored on the instance (p_res_list, d_res_list, ...).
 
@@ -493,8 +601,17 @@ class ADMM_algorithm():
         ``sample_params``: per-sample ADMM weights -- a dict with any of rho, rho_u, rho_d, mu_u, mu_d1, mu_d2, each a 1-D
         sequence / tensor of length B (a name that is missing uses the instance's scalar): sample b solves with its own
         weights and equals the B = 1 solve of an instance carrying them, bit for bit.  For this call only.  LDS-resident
-        float32 path only; with ``check_stop`` it needs ``admm_convergence='per_sample'`` (see ``sweep``)."""
+        float32 path only; with ``check_stop`` it needs ``admm_convergence='per_sample'`` (see ``sweep``).
+
+        ``graph_params``: per-sample graph weights -- a dict with u_sigma and / or d_sigma, each a 1-D sequence / tensor of
+        length B (a name that is missing follows the instance's value): the tables of every distinct pair are built from
+        ``connect_list`` and ``dist_list`` by the constructor's code, and sample b solves on the graph of its pair -- equal to
+        the B = 1 solve of an instance constructed with that pair, bit for bit.  The neighbour lists stay the instance's.
+        ``graph_sets`` / ``graph_of_sample``: the low-level form -- a list of (u_ew, d_ew) tables of the instance's shapes
+        and the index of every sample's set.  For this call only, together with ``sample_params`` if wanted; the same scope
+        and refusals (LDS-resident float32 path, not for a line graph; ValueError or MgadmmError)."""
         sp = _check_sample_params(sample_params, y.shape[0]) if sample_params is not None else None
+        gs = self._check_graph_sets(graph_sets, graph_of_sample, graph_params, y.shape[0])
         if differential:
             assert mask is None, 'differential mode does not support mask'   # flag has no other effect (Q3)
         dt = self._dtype_for(y)
@@ -544,7 +661,7 @@ class ADMM_algorithm():
             be = np.full((I, 3, K, B), np.nan, dtype=np.float64)
             hs.cg_alpha = al.ctypes.data_as(C.POINTER(C.c_double))
             hs.cg_beta = be.ctypes.data_as(C.POINTER(C.c_double))
-        with self._sample_table(h, sp, B):
+        with self._sample_table(h, sp, B), self._graph_table(h, Cn, gs, B):
             if warm_start is None:
                 rc = _lib.lib.mgadmm_solve(h, _ptr(yd), _ptr(md), mask_f32, B, _ptr(x), C.byref(st), C.byref(hs),
                                            _stream_ptr(dev))
@@ -589,15 +706,17 @@ class ADMM_algorithm():
         self.state["x"] = xo
         return xo, (zu, zd), phi, self.history()
 
-    def combined_loop(self, y, mask=None, differential=False, print_info=True, sample_params=None):
+    def combined_loop(self, y, mask=None, differential=False, print_info=True, sample_params=None, **graph_kw):
         """``y`` (B, t_in, N, C) [or (B, T, N, C) with ``mask``] -> ``x`` (B, T, N, C), dtype/device of y.
-        History attributes are filled like the reference's (ADMM.py:612-643).  ``sample_params``: see ``solve``."""
+        History attributes are filled like the reference's (ADMM.py:612-643).  ``sample_params`` and the graph arguments
+        (``graph_params``, ``graph_sets``, ``graph_of_sample``): see ``solve``."""
         return self.solve(y, mask=mask, differential=differential, print_info=print_info, return_state=False,
-                          sample_params=sample_params)[0]
+                          sample_params=sample_params, **graph_kw)[0]
 
     def sweep(self, y, grid, mask=None, chunk=None, **solve_kw):
-        """A grid search over ADMM weights as one batch (the reference's notebooks run one ``combined_loop`` per value).
-        ``y``: W windows; ``grid``: dict name -> list of values.  The Cartesian product of the lists (P sets, in
+        """A grid search over ADMM weights and graph sigmas as one batch (the reference's notebooks run one ``combined_loop``
+        per value).  ``y``: W windows; ``grid``: dict name -> list of values, the names out of the six ADMM weights and
+        ``u_sigma`` / ``d_sigma`` (``solve(graph_params=...)``: one graph per distinct pair, the instance's neighbour lists).  The Cartesian product of the lists (P sets, in
         ``itertools.product`` order of the dict's key order) times the W windows is solved as a batch of P * W samples,
         window index fastest -- in consecutive pieces of at most ``chunk`` samples when ``chunk`` is given.  Returns
         ``(x, n_iters, sets)``: x of shape (P, W, T, N, C), n_iters (P, W) int32 (the iterations of every cell: they differ
@@ -606,8 +725,8 @@ class ADMM_algorithm():
         ``admm_convergence='per_sample'``; without it every cell runs ``max_ADMM_iter`` iterations."""
         names = list(grid)
         for nm in names:
-            if nm not in SAMPLE_PARAM_NAMES:
-                raise ValueError(f"sweep: unknown key {nm!r} (expected some of {SAMPLE_PARAM_NAMES})")
+            if nm not in SAMPLE_PARAM_NAMES + GRAPH_PARAM_NAMES:
+                raise ValueError(f"sweep: unknown key {nm!r} (expected some of {SAMPLE_PARAM_NAMES + GRAPH_PARAM_NAMES})")
         sets = [dict(zip(names, vals)) for vals in itertools.product(*[list(grid[nm]) for nm in names])]
         W, P = y.shape[0], len(sets)
         total = P * W
@@ -619,8 +738,10 @@ class ADMM_algorithm():
         for s0 in range(0, total, step):
             s = np.arange(s0, min(total, s0 + step))             # sample s = set s // W on window s % W
             w = torch.from_numpy(s % W)
-            sp = {nm: [float(sets[j // W][nm]) for j in s] for nm in names}
-            xs.append(self.solve(y[w], mask=None if mask is None else mask[w], sample_params=sp, **solve_kw)[0])
+            sp = {nm: [float(sets[j // W][nm]) for j in s] for nm in names if nm in SAMPLE_PARAM_NAMES}
+            gp = {nm: [float(sets[j // W][nm]) for j in s] for nm in names if nm in GRAPH_PARAM_NAMES}
+            kw = dict(solve_kw, graph_params=gp) if gp else solve_kw
+            xs.append(self.solve(y[w], mask=None if mask is None else mask[w], sample_params=sp, **kw)[0])
             ns.append(np.array(self.n_iters_per_sample, dtype=np.int32))
         x = torch.cat(xs, 0)
         return x.reshape((P, W) + tuple(x.shape[1:])), np.concatenate(ns).reshape(P, W), sets

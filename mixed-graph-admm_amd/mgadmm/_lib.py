@@ -94,6 +94,7 @@ SYMBOLS = {
     "mgadmm_solver_destroy": (C.c_int, [_vp]),
     "mgadmm_solver_set_params": (C.c_int, [_vp, C.POINTER(Params)]),
     "mgadmm_solver_set_sample_params": (C.c_int, [_vp, C.POINTER(SampleParams), C.c_int32]),
+    "mgadmm_solver_set_sample_graphs": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp), _i32p, C.c_int32]),
     "mgadmm_solver_workspace_bytes": (C.c_int64, [_vp]),
     "mgadmm_solver_path": (C.c_int, [_vp, C.c_int32]),
     "mgadmm_solver_query": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int64)]),
