@@ -4,6 +4,7 @@
     files -> TrafficDataset (series resident on the GPU) -> kNN graph -> ADMM_algorithm
           -> prediction of the next 12 steps for a whole batch of sliding windows
           -> grid search over two ADMM weights on the first 16 windows, all cells in one batch
+          -> comparison of three rho ramps (weights that change per ADMM iteration) x mu_d1, again one batch
           -> interpolation of 40 % masked entries
 
 The PEMS files are not redistributable, so the script writes a synthetic PEMS-shaped data set (distance csv,
@@ -99,8 +100,8 @@ def main():
     # the notebooks' grid search (one combined_loop per value there): 3 x 3 sets of (mu_u, mu_d1) on the first 16 windows as ONE
     # batch of 144 samples, every sample with its own weights
     nw = min(16, args.batch)
-    grid = {"mu_u": [0.5 * admm_info["mu_u"], admm_info["mu_u"], 2 * admm_info["mu_u"]],
-            "mu_d1": [0.5 * admm_info["mu_d1"], admm_info["mu_d1"], 2 * admm_info["mu_d1"]]}
+    grid_mu_d1 = [0.5 * admm_info["mu_d1"], admm_info["mu_d1"], 2 * admm_info["mu_d1"]]
+    grid = {"mu_u": [0.5 * admm_info["mu_u"], admm_info["mu_u"], 2 * admm_info["mu_u"]], "mu_d1": grid_mu_d1}
     blk._reset_history()
     blk.admm_convergence = "per_sample"                           # the stop test of a sweep: every cell on its own residuals
     torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -128,6 +129,28 @@ def main():
     print("  u_sigma \\ mu_u " + "".join(f"{v:>9.3g}" for v in grid["mu_u"]))
     for i, a in enumerate(grid["u_sigma"]):
         print(f"  {a:>14.3g} " + "".join(f"{mae[i * 3 + j]:>9.3f}" for j in range(3)))
+
+    # a varying penalty, the first thing anyone tunes in ADMM: rho, rho_u and rho_d ramped TOGETHER by a factor per iteration
+    # (held after 30 rows), 3 factors x 3 values of mu_d1 on the same windows, again ONE batch with per-sample stopping --
+    # column s of the (30, B) schedule is the ramp of sample s's cell; without the schedule every candidate is its own chain of
+    # one-iteration solves
+    from mgadmm.ADMM import geometric_ramp
+    factors, mus = [1.0, 1.05, 1.1], grid_mu_d1
+    cells = [(f, m) for f in factors for m in mus]                # cell p on window w: sample p * nw + w
+    sched = {nm: np.stack([geometric_ramp(admm_info[nm], f, 30) for f, _ in cells for _ in range(nw)], axis=1)
+             for nm in ("rho", "rho_u", "rho_d")}
+    blk._reset_history()
+    blk.admm_convergence = "per_sample"
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    blk.solve(y[:nw].repeat(len(cells), 1, 1, 1), return_state=False, param_schedule=sched,
+              sample_params={"mu_d1": [m for _, m in cells for _ in range(nw)]})
+    torch.cuda.synchronize(); dt = time.perf_counter() - t0
+    blk.admm_convergence = "whole_batch"
+    n_it = np.asarray(blk.n_iters_per_sample).reshape(len(cells), nw)
+    print(f"rho ramps: {len(cells)} cells x {nw} windows in {dt * 1e3:.1f} ms; mean ADMM iterations to the tolerance {blk.ADMM_tol:g} per cell")
+    print("  factor \\ mu_d1 " + "".join(f"{v:>9.3g}" for v in mus))
+    for i, f in enumerate(factors):
+        print(f"  {f:>14.3g} " + "".join(f"{n_it[i * 3 + j].mean():>9.1f}" for j in range(3)))
 
     ix, iy, mask = ds.get_interpolated_batch(starts, 0.4)
     blk._reset_history()

@@ -158,7 +158,7 @@ typedef struct mgadmm_solver mgadmm_solver;
  * mgadmm_params gained cg_convergence and max_inner_iter; 0.3: mgadmm_params gained admm_convergence, mgadmm_history gained
  * n_iters_per_sample): a caller built against an older header must be rebuilt -- compare the string before passing structs.
  * The patch number counts additions that leave every struct alone (0.3.1: mgadmm_solver_set_sample_params;
- * 0.3.2: mgadmm_solver_set_sample_graphs). */
+ * 0.3.2: mgadmm_solver_set_sample_graphs; 0.3.3: mgadmm_solver_set_param_schedule). */
 const char* mgadmm_version(void);
 const char* mgadmm_last_error(void);
 
@@ -218,6 +218,32 @@ int mgadmm_solver_set_sample_params(mgadmm_solver* s, const mgadmm_sample_params
  * solver's own graph. */
 int mgadmm_solver_set_sample_graphs(mgadmm_solver* s, int32_t n_sets, mgadmm_graph* const* graphs, const int32_t* set_of_sample,
                                     int32_t B);
+/* Per-iteration ADMM weights (a rho ramp, the weights of an unrolled network): a table of n_rows rows of the six weights of
+ * ADMM_info.  Iteration k (k = 0, 1, ...) of the following mgadmm_solve / mgadmm_solve_from calls reads row
+ * min(first_row + k, n_rows - 1): the last row holds for the rest of the solve, and first_row lets a resumed solve
+ * (mgadmm_solve_from) continue where the call before it ended.  Host arrays of doubles, each NULL or [n_rows][B] row-major. */
+typedef struct {
+    const double *rho, *rho_u, *rho_d, *mu_u, *mu_d1, *mu_d2;
+} mgadmm_param_schedule;
+/* Two forms.  B >= 1, the per-sample form: sample b reads column b (a comparison of ramps as one batch); the solves must have
+ * this B.  B == 0, the shared form: arrays of [n_rows], every sample reads the same row.  A NULL array follows the table of
+ * mgadmm_solver_set_sample_params if one is set, otherwise the scalar of mgadmm_params; a weight given both here and in that
+ * table -> MGADMM_ERR_INVALID ("given twice"), whichever call comes second.  sch == NULL (or n_rows == 0) clears.  The arrays
+ * are copied.  Synchronous (it waits for the device before an old table is freed).  n_rows < 1, B outside [0, max_batch],
+ * first_row < 0, a value that is not finite, rho / rho_u / rho_d <= 0 or mu_* < 0 -> MGADMM_ERR_INVALID (the message names the
+ * field and [row][b]).  A (row, sample) solves with exactly the floats a solve with those six scalars reads: K scheduled
+ * iterations equal, bit for bit, K solves of one iteration chained by mgadmm_solve_from with the rows set as scalars.
+ * While a schedule is set (decided when a solve starts, before anything runs; the messages contain "param_schedule"):
+ *   - LDS-resident float32 path: both forms; the launches take the kernels k_admm_lds_pp (MGADMM_Q_LDS_UNIT = 2) and keep
+ *     running up to 16 iterations each;
+ *   - streaming path (float32 and float64): the shared form; the per-sample form -> MGADMM_ERR_UNSUPPORTED, as for
+ *     mgadmm_solver_set_sample_params (MGADMM_PATH_STREAM, MGADMM_F64, MGADMM_CG_BATCH_MAX, a graph the LDS path cannot hold);
+ *   - the per-sample form with another B -> MGADMM_ERR_INVALID; with check_stop = 1 and MGADMM_ADMM_WHOLE_BATCH
+ *     -> MGADMM_ERR_UNSUPPORTED.  The shared form stops on the whole-batch test as a solve without a schedule does (every
+ *     sample solves the same problem).
+ * mgadmm_two_loops and the fine-grained entry points (mgadmm_lhs, mgadmm_cg, mgadmm_phi_direct, mgadmm_apply) IGNORE the
+ * schedule: they keep using the scalars of mgadmm_params. */
+int mgadmm_solver_set_param_schedule(mgadmm_solver* s, const mgadmm_param_schedule* sch, int32_t n_rows, int32_t B, int32_t first_row);
 /* bytes of device workspace held by the solver */
 int64_t mgadmm_solver_workspace_bytes(const mgadmm_solver* s);
 /* which path (MGADMM_PATH_STREAM / MGADMM_PATH_LDS) a batch of size B would take */

@@ -56,6 +56,11 @@ int mgadmm_solver_set_sample_graphs(mgadmm_solver* s, int32_t n_sets, mgadmm_gra
     return s->eng->set_sample_graphs(n_sets, graphs, set_of_sample, B);
 }
 
+int mgadmm_solver_set_param_schedule(mgadmm_solver* s, const mgadmm_param_schedule* sch, int32_t n_rows, int32_t B, int32_t first_row) {
+    MG_REQUIRE(s, "set_param_schedule: null solver");
+    return s->eng->set_param_schedule(sch, n_rows, B, first_row);
+}
+
 int64_t mgadmm_solver_workspace_bytes(const mgadmm_solver* s) { return s ? s->eng->workspace_bytes() : 0; }
 int mgadmm_solver_path(const mgadmm_solver* s, int32_t B) { return s ? s->eng->path_for(B) : MGADMM_ERR_INVALID; }
 

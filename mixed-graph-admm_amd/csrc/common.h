@@ -98,6 +98,7 @@ struct EngineBase {
     virtual int set_params(const mgadmm_params& p) = 0;
     virtual int set_sample_params(const mgadmm_sample_params* sp, int B) = 0;
     virtual int set_sample_graphs(int n_sets, mgadmm_graph* const* graphs, const int32_t* set_of_sample, int B) = 0;
+    virtual int set_param_schedule(const mgadmm_param_schedule* sch, int n_rows, int B, int first_row) = 0;
     virtual int64_t workspace_bytes() const = 0;
     virtual int path_for(int B) const = 0;
     virtual int query(int what, int64_t* out) const = 0;

@@ -17,15 +17,10 @@
 #include "lds_args.h"
 #include "lds_plan.h"
 #include "lds_graph_sets.h"
+#include "lds_param_table.h"
 #include "lds_schedule.h"
 
 namespace {
-
-struct LhsDef {
-    int kind;  // 0 diagonal only, 1 cLdr = Ldr^T Ldr, 2 Lu
-    int hth;   // include the observation operator H^T H
-    double c1, c2;
-};
 
 enum VecId {
     V_XA, V_XB, V_ZUA, V_ZUB, V_ZDA, V_ZDB, V_PHIA, V_PHIB, V_GAM, V_GU, V_GD, V_Y, V_MASK,
@@ -101,6 +96,15 @@ struct Engine : EngineBase {
     int sp_B = 0;                 // samples of the table; 0 = none set
     std::vector<double> sp_val[6];   // rho, rho_u, rho_d, mu_u, mu_d1, mu_d2
     LdsSampleParams* d_sp = nullptr;   // [Bmax]
+    // per-iteration weights (mgadmm_solver_set_param_schedule, lds_param_table.h): the caller's arrays ([sch_rows][sch_B], or
+    // [sch_rows] in the shared form sch_B = 0; empty = the weight follows the per-sample table or the scalar) and the device table
+    // of sch_rows x B records, formed when a solve starts and kept until something it was formed from changes
+    int sch_rows = 0;             // rows of the schedule; 0 = none set
+    int sch_B = 0, sch_row0 = 0;
+    std::vector<double> sch_val[6];
+    LdsSampleParams* d_sch = nullptr;
+    size_t sch_elems = 0;
+    int sch_up_B = 0;             // batch the device table was formed for; 0 = it has to be formed
     // per-sample graph weights (mgadmm_solver_set_sample_graphs, lds_graph_sets.h): the images of the sets back to back and the
     // set of every sample; the solver's own image and the planner's switches are kept for the comparison with every set
     int sg_B = 0, sg_sets = 0;    // samples / sets of the table; sg_B = 0: none set
@@ -141,7 +145,7 @@ struct Engine : EngineBase {
         fr(vec_pool); fr(partials); fr(d_rr); fr(d_alpha); fr(d_beta); fr(d_alpha_hist); fr(d_beta_hist);
         fr(d_active); fr(d_iters_tmp); fr(d_nact); fr(d_nonfinite); fr(d_ps); fr(d_hist); fr(d_dxps);
         fr(d_dxpart); fr(d_hist_ps); fr(d_cg_iters); fr(d_lds_csr); fr(d_m2); fr(d_stop); fr(d_ps_ring); fr(d_pstop); fr(d_ps_full);
-        fr(d_sp); fr(d_sg_img); fr(d_sg_set);
+        fr(d_sp); fr(d_sg_img); fr(d_sg_set); fr(d_sch);
         for (float* b : lds_ring_extra) if (b) (void)hipFree(b);
         if (st_side) (void)hipStreamDestroy(st_side);
         for (auto& e : ev_main) if (e) (void)hipEventDestroy(e);
@@ -543,6 +547,9 @@ struct Engine : EngineBase {
             return MGADMM_ERR_UNSUPPORTED;
         }
         MG_TRY(check_admm_convergence(np, "set_params"));
+        if (np.rho != p.rho || np.rho_u != p.rho_u || np.rho_d != p.rho_d || np.mu_u != p.mu_u || np.mu_d1 != p.mu_d1 ||
+            np.mu_d2 != p.mu_d2 || np.ablation != p.ablation)
+            sch_up_B = 0;      // (the schedule's records follow the scalars where it names no weight)
         p = np;
         sv->p = np;
         MG_HIP(hipSetDevice(g->device));
@@ -555,11 +562,18 @@ struct Engine : EngineBase {
         if (sp == nullptr || B == 0) {
             sp_B = 0;
             for (auto& v : sp_val) v.clear();
+            sch_up_B = 0;
             return MGADMM_OK;
         }
         MG_REQUIRE(B >= 1 && B <= Bmax, "set_sample_params: batch %d outside [1, max_batch=%d]", B, Bmax);
         static const char* const names[6] = {"rho", "rho_u", "rho_d", "mu_u", "mu_d1", "mu_d2"};
         const double* const src[6] = {sp->rho, sp->rho_u, sp->rho_d, sp->mu_u, sp->mu_d1, sp->mu_d2};
+        if (sch_rows > 0) {
+            const bool in_sched[6] = {!sch_val[0].empty(), !sch_val[1].empty(), !sch_val[2].empty(), !sch_val[3].empty(),
+                                      !sch_val[4].empty(), !sch_val[5].empty()};
+            const char* twice = ldsparam::given_twice(in_sched, src);
+            MG_REQUIRE(!twice, "set_sample_params: %s is given twice, in the param_schedule that is set and in sample_params", twice);
+        }
         for (int f = 0; f < 6; ++f) {
             if (!src[f]) continue;
             for (int b = 0; b < B; ++b) {
@@ -574,6 +588,7 @@ struct Engine : EngineBase {
             else sp_val[f].clear();
         }
         sp_B = B;
+        sch_up_B = 0;
         MG_HIP(hipSetDevice(g->device));
         return upload_sample_params();
     }
@@ -582,17 +597,8 @@ struct Engine : EngineBase {
     // (n records; without a weights table -- a solve with a graph table alone -- every record holds the scalars)
     int upload_sample_params() { return upload_sample_params(sp_B); }
     int upload_sample_params(int n) {
-        std::vector<LdsSampleParams> rec((size_t)n);
-        const double scalar[6] = {p.rho, p.rho_u, p.rho_d, p.mu_u, p.mu_d1, p.mu_d2};
-        for (int b = 0; b < n; ++b) {
-            double w[6];
-            for (int f = 0; f < 6; ++f) w[f] = sp_val[f].empty() ? scalar[f] : sp_val[f][(size_t)b];
-            const LhsDef dx = lhs_def_of(MGADMM_LHS_X, p.ablation, w[0], w[1], w[2], w[3], w[5]);
-            LdsSampleParams& r = rec[(size_t)b];
-            r.cx1 = (float)dx.c1; r.cx2 = (float)dx.c2;
-            r.rho = (float)w[0]; r.rho_u = (float)w[1]; r.rho_d = (float)w[2];
-            r.mu_u = (float)w[3]; r.mu_d1 = (float)w[4]; r.mu_d2 = (float)w[5];
-        }
+        std::vector<LdsSampleParams> rec;
+        ldsparam::fill_records(weight_source(false), p.ablation, n, rec);      // (lds_param_table.h: one row, no schedule)
         if (!d_sp) MG_HIP(hipMalloc(&d_sp, sizeof(LdsSampleParams) * (size_t)Bmax));
         MG_HIP(hipMemcpy(d_sp, rec.data(), sizeof(LdsSampleParams) * rec.size(), hipMemcpyHostToDevice));
         return MGADMM_OK;
@@ -616,6 +622,97 @@ struct Engine : EngineBase {
                          "the residuals of different problems); or run a fixed count with check_stop = 0");
             return MGADMM_ERR_UNSUPPORTED;
         }
+        return MGADMM_OK;
+    }
+
+    // ---------------------------------------------------------------- per-iteration weights
+    // where a (row, sample) takes its six weights from (lds_param_table.h): the schedule if `with_schedule`, the per-sample
+    // table, the scalars
+    ldsparam::Source weight_source(bool with_schedule) const {
+        ldsparam::Source src;
+        const double scalar[6] = {p.rho, p.rho_u, p.rho_d, p.mu_u, p.mu_d1, p.mu_d2};
+        for (int f = 0; f < 6; ++f) {
+            src.scalar[f] = scalar[f];
+            src.sample[f] = sp_B > 0 && !sp_val[f].empty() ? sp_val[f].data() : nullptr;
+            src.sched[f] = with_schedule && sch_rows > 0 && !sch_val[f].empty() ? sch_val[f].data() : nullptr;
+        }
+        if (with_schedule && sch_rows > 0) { src.n_rows = sch_rows; src.sched_B = sch_B; }
+        return src;
+    }
+
+    // Iteration k of the following solves reads row min(first_row + k, n_rows - 1) of the six arrays ([n_rows][B] row-major, or
+    // [n_rows] with B == 0: every sample reads the same row); a null array follows the per-sample table or the scalar.
+    // Synchronous like set_sample_graphs: the old device table is freed after the device has finished whatever read it.
+    int set_param_schedule(const mgadmm_param_schedule* sch, int n_rows, int B, int first_row) override {
+        MG_HIP(hipSetDevice(g->device));
+        if (sch == nullptr || n_rows == 0) {
+            if (d_sch) {
+                MG_HIP(hipDeviceSynchronize());
+                (void)hipFree(d_sch);
+                d_sch = nullptr;
+                sch_elems = 0;
+            }
+            sch_rows = sch_B = sch_row0 = sch_up_B = 0;
+            for (auto& v : sch_val) v.clear();
+            return MGADMM_OK;
+        }
+        MG_REQUIRE(n_rows >= 1 && n_rows <= (1 << 20), "set_param_schedule: n_rows %d outside [1, 2^20]", n_rows);
+        MG_REQUIRE(B >= 0 && B <= Bmax, "set_param_schedule: batch %d outside [0 (shared form), max_batch=%d]", B, Bmax);
+        MG_REQUIRE(first_row >= 0, "set_param_schedule: first_row %d is negative", first_row);
+        MG_REQUIRE((int64_t)n_rows * Bmax <= (int64_t)1 << 27, "set_param_schedule: n_rows %d x max_batch %d records exceed 2^27", n_rows, Bmax);
+        const double* const src[6] = {sch->rho, sch->rho_u, sch->rho_d, sch->mu_u, sch->mu_d1, sch->mu_d2};
+        std::string why;
+        if (!ldsparam::validate("set_param_schedule: param_schedule", src, n_rows, B, why)) {
+            mg_set_error("%s", why.c_str());
+            return MGADMM_ERR_INVALID;
+        }
+        if (sp_B > 0) {
+            const bool in_table[6] = {!sp_val[0].empty(), !sp_val[1].empty(), !sp_val[2].empty(), !sp_val[3].empty(), !sp_val[4].empty(),
+                                      !sp_val[5].empty()};
+            const char* twice = ldsparam::given_twice(src, in_table);
+            MG_REQUIRE(!twice, "set_param_schedule: %s is given twice, in param_schedule and in the sample_params table that is set", twice);
+        }
+        const size_t n = (size_t)n_rows * (B > 0 ? B : 1);
+        for (int f = 0; f < 6; ++f) {
+            if (src[f]) sch_val[f].assign(src[f], src[f] + n);
+            else sch_val[f].clear();
+        }
+        sch_rows = n_rows; sch_B = B; sch_row0 = first_row; sch_up_B = 0;
+        return MGADMM_OK;
+    }
+
+    // A solve with a schedule set: decided when the solve starts, before anything is enqueued.  The per-sample form is read by
+    // the LDS-resident kernel only (the refusals of check_sample_params); the shared form runs on both paths and with the
+    // whole-batch stop test (every sample solves the same problem)
+    int check_param_schedule(int B) const {
+        if (sch_B == 0) return MGADMM_OK;
+        MG_REQUIRE(B == sch_B, "solve: the param_schedule table holds %d samples per row, the solve has B = %d", sch_B, B);
+        const char* why = nullptr;
+        if (!std::is_same<S, float>::value) why = "float64 arithmetic runs on the streaming path";
+        else if (p.path == MGADMM_PATH_STREAM) why = "path is MGADMM_PATH_STREAM";
+        else if (p.cg_convergence == MGADMM_CG_BATCH_MAX) why = "cg_convergence batch_max runs on the streaming path";
+        else if (!lds.ok) why = "the LDS-resident path cannot hold this graph (it needs T*N*8 B + tables <= 160 KiB and N*G <= 1024)";
+        if (why) {
+            mg_set_error("solve: the per-sample form of param_schedule (one column per sample) is implemented by the LDS-resident float32 "
+                         "path only: %s; the shared form (B = 0) runs on both paths", why);
+            return MGADMM_ERR_UNSUPPORTED;
+        }
+        if (p.check_stop && p.admm_convergence == MGADMM_ADMM_WHOLE_BATCH) {
+            mg_set_error("solve: the per-sample form of param_schedule with check_stop needs admm_convergence per_sample (the whole_batch "
+                         "stop test would sum the residuals of different problems); or run a fixed count with check_stop = 0");
+            return MGADMM_ERR_UNSUPPORTED;
+        }
+        return MGADMM_OK;
+    }
+
+    // the device table of a solve of B samples on the LDS path: sch_rows x B records
+    int upload_param_schedule(int B) {
+        if (sch_up_B == B && d_sch) return MGADMM_OK;
+        std::vector<LdsSampleParams> rec;
+        ldsparam::fill_records(weight_source(true), p.ablation, B, rec);
+        MG_TRY(grow(d_sch, sch_elems, rec.size()));
+        MG_HIP(hipMemcpy(d_sch, rec.data(), sizeof(LdsSampleParams) * rec.size(), hipMemcpyHostToDevice));
+        sch_up_B = B;
         return MGADMM_OK;
     }
 
@@ -974,17 +1071,7 @@ struct Engine : EngineBase {
         return MGADMM_OK;
     }
 
-    LhsDef lhs_def(int which) const { return lhs_def_of(which, p.ablation, p.rho, p.rho_u, p.rho_d, p.mu_u, p.mu_d2); }
-    static LhsDef lhs_def_of(int which, int ablation, double rho, double rho_u, double rho_d, double mu_u, double mu_d2) {
-        switch (which) {
-            case MGADMM_LHS_X:
-                if (ablation == MGADMM_ABL_NONE) return {1, 1, (rho_u + rho_d) / 2, rho / 2};
-                if (ablation == MGADMM_ABL_DGLR) return {1, 1, rho_u / 2, rho / 2};
-                return {0, 1, (rho_u + rho_d) / 2, 0.0};
-            case MGADMM_LHS_ZU: return {2, 0, rho_u / 2, mu_u};
-            default: return {1, 0, rho_d / 2, mu_d2};
-        }
-    }
+    LhsDef lhs_def(int which) const { return lhs_def_of(which, p.ablation, p.rho, p.rho_u, p.rho_d, p.mu_u, p.mu_d2); }      // (lds_param_table.h)
 
     // ---------------------------------------------------------------- operators (internal layout)
     int op_store(const Geom& q, const OpDesc& op, const S* in, S* out, int tag = 2) {
@@ -1322,6 +1409,7 @@ struct Engine : EngineBase {
         st = s;
         if (sp_B > 0) MG_TRY(check_sample_params(B));
         if (sg_B > 0) MG_TRY(check_sample_graphs(B));
+        if (sch_rows > 0) MG_TRY(check_param_schedule(B));
         if (p.path == MGADMM_PATH_LDS && !lds.ok) {
             mg_set_error("solve: the LDS-resident path needs float32, T*N*8 B + CSR <= 160 KiB and N*G <= 1024 (N=%d, T=%d)", N, T);
             return MGADMM_ERR_UNSUPPORTED;
@@ -1376,10 +1464,15 @@ struct Engine : EngineBase {
             MG_HIP(hipMemcpyAsync(vec[zdc], vec[xc], ne * sizeof(S), hipMemcpyDeviceToDevice, st));
         }
 
-        const S rho = (S)p.rho, rho_u = (S)p.rho_u, rho_d = (S)p.rho_d;
+        // the six weights of an iteration: the row of the schedule (shared form: check_param_schedule) or the scalars of `p`
+        const ldsparam::Source wsrc = weight_source(true);
         int n_done = 0;
         int rc_final = MGADMM_OK;
         for (int it = 0; it < max_it; ++it) {
+            double w[6];
+            ldsparam::row_weights(wsrc, it, sch_row0, w);
+            const S rho = (S)w[0], rho_u = (S)w[1], rho_d = (S)w[2];
+            auto lhs_of = [&](int which) { return lhs_def_of(which, p.ablation, w[0], w[1], w[2], w[3], w[5]); };
             // ---- RHS_x (ADMM.py:556-564)
             if (has_phi) {
                 MG_TRY(rows<EpiLin2>(q, op_none(), vec[V_GAM], nullptr, 3, 3, (const S*)vec[phc], vec[V_TMP], (S)1, rho));
@@ -1393,14 +1486,14 @@ struct Engine : EngineBase {
             }
             // ---- x, zu, zd CG solves (ADMM.py:571-592)
             int* it_base = d_cg_iters + (size_t)it * 3 * q.Bp;
-            MG_TRY(cg_internal(q, lhs_def(MGADMM_LHS_X), vec[V_RHS], vec[xc], m, vec[xn], it_base, record));
+            MG_TRY(cg_internal(q, lhs_of(MGADMM_LHS_X), vec[V_RHS], vec[xc], m, vec[xn], it_base, record));
             if (record) MG_TRY(save_coeffs(q, hist, it, 0, B));
-            MG_TRY(rows<EpiLin2>(q, op_none(), vec[V_GU], nullptr, 3, 3, (const S*)vec[xn], vec[V_RHS], (S)0.5, (S)(p.rho_u / 2)));
-            MG_TRY(cg_internal(q, lhs_def(MGADMM_LHS_ZU), vec[V_RHS], vec[zuc], nullptr, vec[zun], it_base + q.Bp, record));
+            MG_TRY(rows<EpiLin2>(q, op_none(), vec[V_GU], nullptr, 3, 3, (const S*)vec[xn], vec[V_RHS], (S)0.5, (S)(w[1] / 2)));
+            MG_TRY(cg_internal(q, lhs_of(MGADMM_LHS_ZU), vec[V_RHS], vec[zuc], nullptr, vec[zun], it_base + q.Bp, record));
             if (record) MG_TRY(save_coeffs(q, hist, it, 1, B));
             if (has_zd) {
-                MG_TRY(rows<EpiLin2>(q, op_none(), vec[V_GD], nullptr, 3, 3, (const S*)vec[xn], vec[V_RHS], (S)0.5, (S)(p.rho_d / 2)));
-                MG_TRY(cg_internal(q, lhs_def(MGADMM_LHS_ZD), vec[V_RHS], vec[zdc], nullptr, vec[zdn], it_base + 2 * q.Bp, record));
+                MG_TRY(rows<EpiLin2>(q, op_none(), vec[V_GD], nullptr, 3, 3, (const S*)vec[xn], vec[V_RHS], (S)0.5, (S)(w[2] / 2)));
+                MG_TRY(cg_internal(q, lhs_of(MGADMM_LHS_ZD), vec[V_RHS], vec[zdc], nullptr, vec[zdn], it_base + 2 * q.Bp, record));
                 if (record) MG_TRY(save_coeffs(q, hist, it, 2, B));
             }
             const S* zd_now = has_zd ? vec[zdn] : vec[zdc];
@@ -1415,7 +1508,7 @@ struct Engine : EngineBase {
             }
             // ---- phi prox, gamma update, Ldr-based residuals and regularisers (ADMM.py:600-606, 627-637)
             MG_TRY(rows<EpiPhi>(q, g->op_ldr(), vec[xn], nullptr, 2, has_phi ? 5 : 1, (const S*)vec[phc], vec[phn], vec[V_GAM],
-                                rho, (S)(p.mu_d1 / p.rho), has_phi ? 1 : 0));
+                                rho, (S)(w[4] / w[0]), has_phi ? 1 : 0));
             {
                 FinMetrics<4> f{d_ps, q.Bp, {has_phi ? MGADMM_M_PRI_PHI : -1, has_phi ? MGADMM_M_DUAL_PHI : -1,
                                             has_phi ? MGADMM_M_DGTV : -1, has_zd ? MGADMM_M_DGLR : -1}};
@@ -1774,9 +1867,9 @@ struct Engine : EngineBase {
             a.J = ch.Jc;
             for (int k = 0; k <= ch.Jc; ++k) a.xs[k] = lds_xbuf(r, ch.it0 + k);
             a.cg_iters = d_cg_iters + (size_t)ch.it0 * 3 * r.Bp;
+            a.it0 = ch.it0;                       // (read with the per-sample stop and with a schedule of weights)
             if (r.s.per_sample) {
                 a.ps = d_ps_full + (size_t)ch.it0 * row;
-                a.it0 = ch.it0;
                 MG_TRY(launch_lds(a, r.B));
                 r.n_done = ch.it0 + ch.Jc;
                 int stopped = 0;
@@ -1807,7 +1900,8 @@ struct Engine : EngineBase {
             a.xs[0] = lds_xbuf(r, it); a.xs[1] = lds_xbuf(r, it + 1);
             a.cg_iters = d_cg_iters + (size_t)it * 3 * r.Bp;
             a.ps = d_ps;
-            if (r.s.per_sample) { a.ps = d_ps_full + (size_t)it * MGADMM_NMETRIC * r.Bp; a.it0 = it; }
+            a.it0 = it;                           // (read with the per-sample stop and with a schedule of weights)
+            if (r.s.per_sample) a.ps = d_ps_full + (size_t)it * MGADMM_NMETRIC * r.Bp;
             if (r.record) {
                 MG_TRY(fill((S*)d_alpha_hist, 3 * K * r.Bp, (S)NAN));
                 MG_TRY(fill((S*)d_beta_hist, 3 * K * r.Bp, (S)NAN));
@@ -1909,6 +2003,11 @@ struct Engine : EngineBase {
                 if (sp_B == 0) MG_TRY(upload_sample_params(B));      // no weights table: records of the scalars, the same kernels
                 r.a.sp = d_sp;
                 r.a.csr = d_sg_img; r.a.img_stride = ldssets::img_stride(lds); r.a.gset = d_sg_set;
+            }
+            if (sch_rows > 0) {               // (check_param_schedule) trip k of a launch reads row sched_row(it0 + k, ...) of sch_rows x B records
+                MG_TRY(upload_param_schedule(B));
+                r.a.sp = d_sch;
+                r.a.sp_rows = sch_rows; r.a.sp_row0 = sch_row0; r.a.sp_stride = B;
             }
             MG_TRY(chunked ? lds_run_chunks(r) : lds_run_steps(r));
             std::vector<int> nps;         // per-sample stop: iterations of every sample

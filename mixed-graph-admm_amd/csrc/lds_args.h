@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lds_consts.h"     // LDS_NLEAD, LDS_MAXJ, lds_instance_key
+#include "lds_param_table.h"   // LdsSampleParams, sched_row
 
 // scalar part of the launch arguments: a trip of the loop inside k_admm_lds reads it from the kernarg segment
 struct LdsArgsCore {
@@ -43,12 +44,6 @@ struct LdsArgsCore {
     const int* stop;       // device stop word of the ADMM outer loop (nullptr: none): a launch enqueued speculatively after the
                            // stop test of an earlier iteration passed returns at its first instruction
 };
-// Per-sample ADMM weights (mgadmm_solver_set_sample_params): one record per workgroup launched, the eight values a trip of
-// k_admm_lds reads from LdsArgsCore, formed by the host from sample b's six doubles with the expressions of the scalars
-struct LdsSampleParams {
-    float rho, rho_u, rho_d, mu_u, mu_d1, mu_d2;
-    float cx1, cx2;
-};
 struct LdsArgs : LdsArgsCore {
     float* xs[LDS_MAXJ + 1];   // trip k reads the iterate xs[k] and writes xs[k + 1] (every iterate is kept: delta_x_per_step);
                                // indexed by the trip number straight from the kernarg segment
@@ -59,11 +54,11 @@ struct LdsArgs : LdsArgsCore {
     int* pstop_count;      // number of samples that have stopped (the host ends the solve when it reads B)
     float* x_final;        // (B, TN): a sample that stops stores its iterate here itself (the iterate buffers of a chunk rotate)
     double admm_tol;       // ADMM_tol
-    int it0;               // number of the launch's first iteration in this solve (n_b = it0 + trip + 1)
+    int it0;               // number of the launch's first iteration in this solve (n_b = it0 + trip + 1; the row of a weight schedule)
     // Per-sample weights (read by the kernels k_admm_lds_pp only, which a launch takes when sp != nullptr; behind everything the
     // other kernels read): workgroup b takes rho .. cx2 from sp[b] instead of the scalars above.  In these kernels the
     // per-sample stop test runs when pstop != nullptr
-    const LdsSampleParams* sp;   // [B] device table
+    const LdsSampleParams* sp;   // [B] device table ([sp_rows][sp_stride] with a schedule of weights, below)
     // Row plan of the uniform-row instances with a compile-time tail (lds_rows.h; read by those instances only; behind everything
     // else: no offset that existing code reads moves)
     unsigned long long npos;     // 4-bit field w: positions of the W_d^T table (leading entries + tail) wave w gathers -- the largest
@@ -74,6 +69,10 @@ struct LdsArgs : LdsArgsCore {
     // weights of set gset[b] (lds_graph_sets.h)
     int img_stride;              // ints between two images
     const int* gset;             // [Bp] device table, or nullptr: every workgroup reads set 0
+    // Per-iteration weights (mgadmm_solver_set_param_schedule, lds_param_table.h; read by the kernels k_admm_lds_pp only; behind
+    // everything else): sp then holds sp_rows rows of records, record row * sp_stride + b, and trip k of the launch reads row
+    // sched_row(it0 + k, sp_row0, sp_rows).  Zero (no schedule): every trip reads sp[b]
+    int sp_rows{}, sp_row0{}, sp_stride{};   // rows of the table, row of the solve's first iteration, records between two rows
 };
 
 // Execution plan of k_admm_lds chosen by ldsplan::make (lds_plan.h)

@@ -868,10 +868,24 @@ __device__ __forceinline__ int lds_cg(LdsCtx<TPG, BAND, NU, ND, TP>& c, BlockRed
 #define MG_LDS_PS true
 #define MG_LDS_PSTOP_ON(args) ((args).pstop != nullptr)
 #if defined(__HIP_DEVICE_COMPILE__)
-#define MG_LDS_W(field) (((const LdsSampleParams __attribute__((address_space(4)))*)a.sp)[b].field)
+#define MG_LDS_W(field) (((const LdsSampleParams __attribute__((address_space(4)))*)a.sp)[wrec].field)
+#define MG_LDS_W_NEXT(field, now) (((const LdsSampleParams __attribute__((address_space(4)))*)a.sp)[MG_LDS_WREC_OF(trip + 1)].field)
+#define MG_LDS_WREC_DECL unsigned wrec = MG_LDS_WREC_OF(trip); MG_PIN_S(wrec)
 #else
-#define MG_LDS_W(field) (a.sp[b].field)
+#define MG_LDS_W(field) (a.sp[wrec].field)
+#define MG_LDS_W_NEXT(field, now) (a.sp[MG_LDS_WREC_OF(trip + 1)].field)
+#define MG_LDS_WREC_DECL const unsigned wrec = MG_LDS_WREC_OF(trip)
 #endif
+// Per-iteration weights (mgadmm_solver_set_param_schedule): the table holds sp_rows rows of records at a stride of sp_stride
+// records, and the trip reads the row of ITS iteration, sched_row (lds_param_table.h) of the launch's first iteration + trip:
+// kernel arguments, the trip counter and the workgroup number only, so the record number is a scalar value formed once per
+// trip (MG_LDS_WREC_DECL, at the head of the trip body) and the loads stay scalar loads.  Without a schedule the three words
+// are 0 and the record is b, as before them.
+// A trip also forms operands of the NEXT trip's RHS_x while their inputs are in registers (o = (rho_u zu - gamma_u) / 2 + ...,
+// v = gamma + rho phi): those products belong to the next iteration and take its rho, rho_u, rho_d -- MG_LDS_W_NEXT(field,
+// now), the record of iteration it0 + trip + 1, read where it is used (three scalar loads per trip, outside the CG loops; the
+// row is clamped, so the read of a launch's last trip, whose operands nobody uses, stays inside the table).  Elsewhere it is `now`.
+#define MG_LDS_WREC_OF(k) ((unsigned)sched_row(a.it0 + (k), a.sp_row0, a.sp_rows) * (unsigned)a.sp_stride + (unsigned)b)
 // Per-sample graph weights (mgadmm_solver_set_sample_graphs): the images of S weight sets of one topology lie back to back
 // at a stride of LdsArgs::img_stride ints, workgroup b reads the one of set gset[b] (no table: set 0).  The base is formed
 // where it is used, from a workgroup-uniform load of the set number through the constant address space like MG_LDS_W: it
@@ -893,6 +907,8 @@ __device__ __forceinline__ int lds_cg(LdsCtx<TPG, BAND, NU, ND, TP>& c, BlockRed
 #endif
 #define MG_LDS_PSTOP_ON(args) true
 #define MG_LDS_W(field) (a.field)
+#define MG_LDS_W_NEXT(field, now) (now)
+#define MG_LDS_WREC_DECL do { } while (0)
 #define MG_LDS_IMG(args) (args).csr
 #endif
 template <int TPG, bool BAND, int MAXT, bool SB, int NU = 0, int ND = 0, bool SLOTS = false, int TP = -1>
@@ -1065,6 +1081,7 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
     const int ty = a.mask ? a.T : a.t_in;
     const float* yb = a.y + (size_t)b * ty * a.N;
     const bool has_phi = a.has_phi, has_zd = a.has_zd;
+    MG_LDS_WREC_DECL;
     const float rho = MG_LDS_W(rho), rho_u = MG_LDS_W(rho_u), rho_d = MG_LDS_W(rho_d);
     const int Nn = a.N;
 
@@ -1320,6 +1337,7 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
         }
         float m_pri = 0.f, m_dual = 0.f;
         float ou[TPG];
+        const float rho_u_next = MG_LDS_W_NEXT(rho_u, rho_u);      // o belongs to the next trip
 #pragma unroll
         for (int k = 0; k < TPG; ++k) {
             xr[k] = c.active ? xr[k] : 0.f;
@@ -1331,7 +1349,7 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
             m_pri += pz * pz;
             m_dual += dz * dz;
             gv[k] = gv[k] + rho_u * pz;
-            ou[k] = rhs_half(rho_u, z[k], gv[k]);
+            ou[k] = rhs_half(rho_u_next, z[k], gv[k]);
         }
         c.puts(zu, z);
         c.puts(gu, gv);
@@ -1385,8 +1403,9 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
             float ou[TPG], yv[TPG];
             request_y(yv);
             slot_get<TPG>(slot1, tid, nthr, ou);
+            const float rho_d_next = MG_LDS_W_NEXT(rho_d, rho_d);
 #pragma unroll
-            for (int k = 0; k < TPG; ++k) ou[k] = c.active ? (ou[k] + rhs_half(rho_d, z[k], gv[k])) + yv[k] : 0.f;
+            for (int k = 0; k < TPG; ++k) ou[k] = c.active ? (ou[k] + rhs_half(rho_d_next, z[k], gv[k])) + yv[k] : 0.f;
             slot_put<TPG>(slot1, tid, nthr, ou);
         }
         mput(MGADMM_M_PRI_ZD, m_pri);
@@ -1416,6 +1435,7 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
         float l[TPG];
         c.op_ldr(P, xr, l, R);
         const float thr = MG_LDS_W(mu_d1) / rho;
+        const float rho_next = MG_LDS_W_NEXT(rho, rho);              // v belongs to the next trip
         float pn[TPG], gnew[TPG];
 #pragma unroll
         for (int k = 0; k < TPG; ++k) {
@@ -1429,7 +1449,7 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
             m_priphi += dd * dd;
             m_dualphi += dp * dp;
             gnew[k] = gv + rho * dd;
-            vc[k] = has_phi ? ldrt_operand(rho, pn[k], gnew[k]) : 0.f;       // v of the next trip (ghosts: gn = zn = l = 0 -> 0)
+            vc[k] = has_phi ? ldrt_operand(rho_next, pn[k], gnew[k]) : 0.f;  // v of the next trip (ghosts: gn = zn = l = 0 -> 0)
             xc[k] = xr[k];                                                    // x_old of the next trip
         }
         if (has_phi) {

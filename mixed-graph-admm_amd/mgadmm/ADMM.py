@@ -23,7 +23,7 @@ from . import _lib
 from . import utils as _u
 from .graph import Graph, expand_channels, tables_to_csr
 
-__all__ = ["ADMM_algorithm", "initial_guess", "initial_interpolation"]
+__all__ = ["ADMM_algorithm", "initial_guess", "initial_interpolation", "geometric_ramp"]
 
 _TORCH2MG = {torch.float32: _lib.F32, torch.float64: _lib.F64}
 _NP = {torch.float32: np.float32, torch.float64: np.float64}
@@ -70,6 +70,54 @@ def _check_sample_params(sample_params, B):
                              + ("rho, rho_u and rho_d must be > 0" if name.startswith("rho") else "mu_u, mu_d1 and mu_d2 must be >= 0"))
         out[name] = v
     return out
+
+
+def _check_param_schedule(param_schedule, B, schedule_start=0, sample_params=None):
+    """``param_schedule`` of ``solve``: dict name -> array of shape (K,) (shared form) or (K, B) (per-sample form), the same K
+    and the same form for every name, as ``(dict name -> float64 array, K, 0 or B)``.  Raises ValueError for an unknown name,
+    a wrong shape, a value that is not finite, rho* <= 0 or mu* < 0 (named by [row][b]), a name that ``sample_params`` gives
+    too, or a negative ``schedule_start`` (what ``mgadmm_solver_set_param_schedule`` refuses, found before the library is
+    touched)."""
+    if not hasattr(param_schedule, "items"):
+        raise ValueError(f"param_schedule must be a dict with keys out of {SAMPLE_PARAM_NAMES}, got {type(param_schedule).__name__}")
+    if int(schedule_start) != schedule_start or schedule_start < 0:
+        raise ValueError(f"schedule_start must be an integer >= 0, got {schedule_start!r}")
+    out, shape = {}, None
+    for name, vals in param_schedule.items():
+        if name not in SAMPLE_PARAM_NAMES:
+            raise ValueError(f"param_schedule: unknown key {name!r} (expected some of {SAMPLE_PARAM_NAMES})")
+        if sample_params is not None and name in sample_params:
+            raise ValueError(f"param_schedule[{name!r}] is given twice: in param_schedule and in sample_params")
+        v = vals.detach().cpu().numpy() if torch.is_tensor(vals) else np.asarray(vals)
+        v = np.ascontiguousarray(v, dtype=np.float64) if v.ndim else v          # (ascontiguousarray turns a scalar into (1,))
+        if v.ndim not in (1, 2) or v.shape[0] < 1 or (v.ndim == 2 and v.shape[1] != B):
+            raise ValueError(f"param_schedule[{name!r}] must have shape (K,) or (K, B = {B}) with K >= 1, got shape {tuple(v.shape)}")
+        if shape is not None and v.shape != shape:
+            raise ValueError(f"param_schedule[{name!r}] has shape {tuple(v.shape)}, the entries before it {tuple(shape)}: "
+                             "one number of rows and one form (shared or per-sample) for all")
+        shape = v.shape
+        at = lambda idx: "".join(f"[{int(i)}]" for i in idx)
+        if not np.isfinite(v).all():
+            raise ValueError(f"param_schedule[{name!r}]{at(np.argwhere(~np.isfinite(v))[0])} is not finite")
+        bad = np.argwhere(v <= 0 if name.startswith("rho") else v < 0)
+        if bad.size:
+            raise ValueError(f"param_schedule[{name!r}]{at(bad[0])} = {v[tuple(bad[0])]}: "
+                             + ("rho, rho_u and rho_d must be > 0" if name.startswith("rho") else "mu_u, mu_d1 and mu_d2 must be >= 0"))
+        out[name] = v
+    if shape is None:
+        return out, 0, 0
+    return out, int(shape[0]), (int(shape[1]) if len(shape) == 2 else 0)
+
+
+def geometric_ramp(v0, factor, n_rows, vmax=None):
+    """Rows of a geometric schedule: ``v0 * factor ** row`` for row = 0 .. n_rows - 1 as a float64 array, capped at ``vmax``
+    when given (``solve(param_schedule={'rho': geometric_ramp(rho, 1.1, 20)})``; the last row holds for the rest of a solve)."""
+    if int(n_rows) != n_rows or n_rows < 1:
+        raise ValueError(f"geometric_ramp: n_rows must be an integer >= 1, got {n_rows!r}")
+    if not (np.isfinite(v0) and np.isfinite(factor) and v0 > 0 and factor > 0):
+        raise ValueError(f"geometric_ramp: v0 and factor must be finite and > 0, got {v0!r}, {factor!r}")
+    v = float(v0) * float(factor) ** np.arange(int(n_rows), dtype=np.float64)
+    return v if vmax is None else np.minimum(v, float(vmax))
 
 
 GRAPH_PARAM_NAMES = ("u_sigma", "d_sigma")
@@ -367,6 +415,23 @@ class ADMM_algorithm():
         finally:
             _lib.lib.mgadmm_solver_set_sample_params(h, None, 0)
 
+    @contextlib.contextmanager
+    def _schedule_table(self, h, sch, first_row):
+        """Per-iteration ADMM weights (``_check_param_schedule`` output) set on solver ``h`` for the solves inside the block and
+        cleared after it, like ``_sample_table``."""
+        if sch is None or not sch[0]:
+            yield
+            return
+        arrays, n_rows, cols = sch
+        sc = _lib.ParamSchedule()
+        for nm, v in arrays.items():
+            setattr(sc, nm, v.ctypes.data_as(C.POINTER(C.c_double)))
+        _lib.check(_lib.lib.mgadmm_solver_set_param_schedule(h, C.byref(sc), n_rows, cols, int(first_row)))
+        try:
+            yield
+        finally:
+            _lib.lib.mgadmm_solver_set_param_schedule(h, None, 0, 0, 0)
+
     def _check_graph_sets(self, graph_sets, graph_of_sample, graph_params, B):
         """The graph arguments of ``solve`` as ``(sets, set_of_sample)`` -- a list of (u_ew, d_ew) tables and an int32 array of
         length B -- or None without them.  ValueError for what can be refused before the library is touched."""
@@ -590,7 +655,8 @@ class ADMM_algorithm():
         return None
 
     def solve(self, y, mask=None, differential=False, print_info=False, return_state=True, per_sample_history=False,
-              warm_start=None, sample_params=None, graph_sets=None, graph_of_sample=None, graph_params=None):
+              warm_start=None, sample_params=None, graph_sets=None, graph_of_sample=None, graph_params=None,
+              param_schedule=None, schedule_start=0):
         """Run the ADMM loop and return ``(x, (zu, zd), phi, history)``; ``history`` is a dict with the
         same lists that are also stored on the instance (p_res_list, d_res_list, ...).
 
@@ -609,8 +675,16 @@ class ADMM_algorithm():
         the B = 1 solve of an instance constructed with that pair, bit for bit.  The neighbour lists stay the instance's.
         ``graph_sets`` / ``graph_of_sample``: the low-level form -- a list of (u_ew, d_ew) tables of the instance's shapes
         and the index of every sample's set.  For this call only, together with ``sample_params`` if wanted; the same scope
-        and refusals (LDS-resident float32 path, not for a line graph; ValueError or MgadmmError)."""
+        and refusals (LDS-resident float32 path, not for a line graph; ValueError or MgadmmError).
+
+        ``param_schedule``: per-iteration ADMM weights -- a dict with any of the six names, each an array of shape (K,) (every
+        sample reads the same row; both paths, float32 and float64, any stop test) or (K, B) (sample b reads column b; the
+        scope of ``sample_params``).  Iteration k of this call solves with row ``min(schedule_start + k, K - 1)``; a name
+        that is missing follows ``sample_params`` or the instance's scalar, a name given in both is refused.  K scheduled
+        iterations equal K one-iteration solves chained with ``warm_start`` and the rows assigned as scalars, bit for bit;
+        ``schedule_start`` lets a resumed solve continue the schedule.  For this call only (``geometric_ramp`` builds a ramp)."""
         sp = _check_sample_params(sample_params, y.shape[0]) if sample_params is not None else None
+        sch = (_check_param_schedule(param_schedule, y.shape[0], schedule_start, sp) if param_schedule is not None else None)
         gs = self._check_graph_sets(graph_sets, graph_of_sample, graph_params, y.shape[0])
         if differential:
             assert mask is None, 'differential mode does not support mask'   # flag has no other effect (Q3)
@@ -661,7 +735,7 @@ class ADMM_algorithm():
             be = np.full((I, 3, K, B), np.nan, dtype=np.float64)
             hs.cg_alpha = al.ctypes.data_as(C.POINTER(C.c_double))
             hs.cg_beta = be.ctypes.data_as(C.POINTER(C.c_double))
-        with self._sample_table(h, sp, B), self._graph_table(h, Cn, gs, B):
+        with self._sample_table(h, sp, B), self._graph_table(h, Cn, gs, B), self._schedule_table(h, sch, schedule_start):
             if warm_start is None:
                 rc = _lib.lib.mgadmm_solve(h, _ptr(yd), _ptr(md), mask_f32, B, _ptr(x), C.byref(st), C.byref(hs),
                                            _stream_ptr(dev))
@@ -706,14 +780,16 @@ class ADMM_algorithm():
         self.state["x"] = xo
         return xo, (zu, zd), phi, self.history()
 
-    def combined_loop(self, y, mask=None, differential=False, print_info=True, sample_params=None, **graph_kw):
+    def combined_loop(self, y, mask=None, differential=False, print_info=True, sample_params=None, param_schedule=None, **graph_kw):
         """``y`` (B, t_in, N, C) [or (B, T, N, C) with ``mask``] -> ``x`` (B, T, N, C), dtype/device of y.
-        History attributes are filled like the reference's (ADMM.py:612-643).  ``sample_params`` and the graph arguments
-        (``graph_params``, ``graph_sets``, ``graph_of_sample``): see ``solve``."""
+        History attributes are filled like the reference's (ADMM.py:612-643).  ``sample_params``, ``param_schedule`` and the
+        graph arguments (``graph_params``, ``graph_sets``, ``graph_of_sample``): see ``solve``."""
+        if param_schedule is not None:
+            graph_kw = dict(graph_kw, param_schedule=param_schedule)
         return self.solve(y, mask=mask, differential=differential, print_info=print_info, return_state=False,
                           sample_params=sample_params, **graph_kw)[0]
 
-    def sweep(self, y, grid, mask=None, chunk=None, **solve_kw):
+    def sweep(self, y, grid, mask=None, chunk=None, schedules=None, **solve_kw):
         """A grid search over ADMM weights and graph sigmas as one batch (the reference's notebooks run one ``combined_loop``
         per value).  ``y``: W windows; ``grid``: dict name -> list of values, the names out of the six ADMM weights and
         ``u_sigma`` / ``d_sigma`` (``solve(graph_params=...)``: one graph per distinct pair, the instance's neighbour lists).  The Cartesian product of the lists (P sets, in
@@ -722,12 +798,30 @@ class ADMM_algorithm():
         ``(x, n_iters, sets)``: x of shape (P, W, T, N, C), n_iters (P, W) int32 (the iterations of every cell: they differ
         with ``admm_convergence='per_sample'``), ``sets`` the list of the P dicts.  Cell (p, w) equals the B = 1 solve of
         window w by an instance carrying ``sets[p]``.  With ``check_stop`` the instance needs
-        ``admm_convergence='per_sample'``; without it every cell runs ``max_ADMM_iter`` iterations."""
+        ``admm_convergence='per_sample'``; without it every cell runs ``max_ADMM_iter`` iterations.
+
+        ``schedules``: dict name -> list of candidate schedules of that weight (1-D arrays of one length K, e.g.
+        ``geometric_ramp``), crossed with ``grid`` after the grid's keys, in the same product order; a set then carries the
+        candidate array under its name, and cell (p, w) runs ``solve(param_schedule=...)`` with column p * W + w holding the
+        candidates of set p (a comparison of ramps as one batch)."""
+        sched_names = list(schedules) if schedules else []
+        for nm in sched_names:
+            if nm not in SAMPLE_PARAM_NAMES:
+                raise ValueError(f"sweep: unknown schedule key {nm!r} (expected some of {SAMPLE_PARAM_NAMES})")
+            if nm in grid:
+                raise ValueError(f"sweep: {nm!r} is given twice: in grid and in schedules")
+        cands = {nm: [np.asarray(c.detach().cpu().numpy() if torch.is_tensor(c) else c, dtype=np.float64) for c in schedules[nm]]
+                 for nm in sched_names}
+        if sched_names:
+            shapes = {c.shape for cs in cands.values() for c in cs}
+            if len(shapes) != 1 or len(next(iter(shapes))) != 1 or next(iter(shapes))[0] < 1:
+                raise ValueError(f"sweep: the candidates of schedules must be 1-D arrays of one length K >= 1, got shapes {sorted(shapes)}")
         names = list(grid)
         for nm in names:
             if nm not in SAMPLE_PARAM_NAMES + GRAPH_PARAM_NAMES:
                 raise ValueError(f"sweep: unknown key {nm!r} (expected some of {SAMPLE_PARAM_NAMES + GRAPH_PARAM_NAMES})")
-        sets = [dict(zip(names, vals)) for vals in itertools.product(*[list(grid[nm]) for nm in names])]
+        sets = [dict(zip(names + sched_names, vals))
+                for vals in itertools.product(*([list(grid[nm]) for nm in names] + [cands[nm] for nm in sched_names]))]
         W, P = y.shape[0], len(sets)
         total = P * W
         step = total if chunk is None else int(chunk)
@@ -741,6 +835,8 @@ class ADMM_algorithm():
             sp = {nm: [float(sets[j // W][nm]) for j in s] for nm in names if nm in SAMPLE_PARAM_NAMES}
             gp = {nm: [float(sets[j // W][nm]) for j in s] for nm in names if nm in GRAPH_PARAM_NAMES}
             kw = dict(solve_kw, graph_params=gp) if gp else solve_kw
+            if sched_names:          # column j of a (K, B) schedule: the candidate of sample j's set
+                kw = dict(kw, param_schedule={nm: np.stack([sets[j // W][nm] for j in s], axis=1) for nm in sched_names})
             xs.append(self.solve(y[w], mask=None if mask is None else mask[w], sample_params=sp, **kw)[0])
             ns.append(np.array(self.n_iters_per_sample, dtype=np.int32))
         x = torch.cat(xs, 0)

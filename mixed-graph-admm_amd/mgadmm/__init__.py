@@ -9,7 +9,7 @@ been built; there is no CPU fallback.
 """
 from . import _lib  # noqa: F401  (raises OSError when the HIP extension is missing)
 from . import utils  # noqa: F401
-from .ADMM import ADMM_algorithm, initial_guess, initial_interpolation  # noqa: F401
+from .ADMM import ADMM_algorithm, geometric_ramp, initial_guess, initial_interpolation  # noqa: F401
 from .CG_script import conjugate_gradient  # noqa: F401
 from .dist import shard_bounds, sharded_solve  # noqa: F401
 from . import gpu_graph  # noqa: F401

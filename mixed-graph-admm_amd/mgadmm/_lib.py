@@ -80,6 +80,9 @@ class SampleParams(C.Structure):
     _fields_ = [("rho", _f64p), ("rho_u", _f64p), ("rho_d", _f64p), ("mu_u", _f64p), ("mu_d1", _f64p), ("mu_d2", _f64p)]
 
 
+ParamSchedule = SampleParams       # mgadmm_param_schedule: the same six pointers, arrays of [n_rows][B] / [n_rows]
+
+
 # every symbol include/mgadmm.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
 SYMBOLS = {
@@ -95,6 +98,7 @@ SYMBOLS = {
     "mgadmm_solver_set_params": (C.c_int, [_vp, C.POINTER(Params)]),
     "mgadmm_solver_set_sample_params": (C.c_int, [_vp, C.POINTER(SampleParams), C.c_int32]),
     "mgadmm_solver_set_sample_graphs": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp), _i32p, C.c_int32]),
+    "mgadmm_solver_set_param_schedule": (C.c_int, [_vp, C.POINTER(SampleParams), C.c_int32, C.c_int32, C.c_int32]),
     "mgadmm_solver_workspace_bytes": (C.c_int64, [_vp]),
     "mgadmm_solver_path": (C.c_int, [_vp, C.c_int32]),
     "mgadmm_solver_query": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int64)]),
