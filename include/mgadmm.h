@@ -267,16 +267,23 @@ typedef enum {
     MGADMM_Q_LDS_SLOTS = 12,    /* 1: two LDS vectors park per-thread operands across the solves                    */
     MGADMM_Q_LDS_CHUNK = 13,    /* ADMM iterations per k_admm_lds launch when the iteration count is fixed          */
     MGADMM_Q_LDS_ROWS = 14,     /* LDS rows of an image: nodes + ghost rows                                         */
-    MGADMM_Q_CLDR_SLOTS = 15,   /* W_d^T entry slots per row of the fused Ldr^T Ldr kernel in use (12 / 16 / 24); 0: two-pass */
+    MGADMM_Q_CLDR_SLOTS = 15,   /* W_d^T entry slots per row of the fused Ldr^T Ldr kernel in use (12 / 16 / 24); 0: two-pass
+                                   form -- the graph does not fit the kernel's tables, or the solver's max_batch (the query
+                                   answers for max_batch, not for the batch of a later call) is no multiple of the kernel's
+                                   chunk width.  Valid after the first operator application                             */
     MGADMM_Q_LDS_CG_BARRIERS = 17,/* workgroup barriers per CG iteration of a cLdr solve (x, zd) in the planned k_admm_lds
                                    instance: 4 (5 in single-buffer mode), or 3 in the uniform-row instances, which form p.Ap
                                    from q.q ahead of the q exchange; 0 without the LDS path                              */
     MGADMM_Q_LDS_INSTANCE = 16, /* template arguments <TPG, BAND, MAXT, SB, NU, ND, SLOTS, TP> of the k_admm_lds instance the
                                    last LDS launch ran, packed: bits 0-7 TPG, 8 BAND, 9 SB, 10 SLOTS, 11-15 NU, 16-20 ND,
                                    21-31 MAXT, 32-39 TP + 1; -1 before the first launch                                   */
-    MGADMM_Q_LDS_UNIT = 18      /* which of the three compilations of the instances the last LDS launch ran: 0 = k_admm_lds,
+    MGADMM_Q_LDS_UNIT = 18,     /* which of the three compilations of the instances the last LDS launch ran: 0 = k_admm_lds,
                                    1 = k_admm_lds_ps (per-sample stop test), 2 = k_admm_lds_pp (per-sample weights); -1 before
                                    the first launch                                                                       */
+    MGADMM_Q_STREAM_KEYS = 19,  /* distinct streaming-path kernel instances (k_rows, k_tile, k_cldr) launched since the solver was
+                                   created (tests: which instance did a problem reach)                                     */
+    MGADMM_Q_STREAM_KEY0 = 1000 /* item 1000 + i: the packed template arguments of the i-th of them in first-launch order
+                                   (csrc/stream_keys.h; mgadmm/_lib.py decode_stream_key); i past the count: MGADMM_ERR_INVALID */
 } mgadmm_query_t;
 int mgadmm_solver_query(const mgadmm_solver* s, int32_t what, int64_t* out);
 

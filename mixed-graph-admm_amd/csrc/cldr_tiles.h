@@ -18,6 +18,21 @@ struct CldrCaps {
     int GD, GT;               // entry slots per W_d row and per W_d^T row
 };
 
+// Tile geometries of k_cldr by number (MGADMM_CLDR_GEOM; engine.h, ClG1 ... ClG4): VECT columns per lane, NW waves, rows per
+// wave of the tile (MA) / of C1 (MQ) / of C2 (MP).  The caps of a geometry are NW * MA, NW * MQ, NW * MP rows.
+struct CldrGeomDims { int VECT, NW, MA, MQ, MP; };
+constexpr CldrGeomDims CLDR_GEOMS[5] = {
+    {0, 0, 0, 0, 0},
+    {4, 8, 2, 4, 5},      // 1: 16 / 32 / 40 rows of 256 columns
+    {1, 8, 8, 11, 15},    // 2: 64 / 88 / 120 rows of 64 columns
+    {2, 8, 4, 8, 10},     // 3: 32 / 64 / 80 rows of 128 columns
+    {4, 16, 2, 3, 4},     // 4: 32 / 48 / 64 rows of 256 columns, 16 waves
+};
+inline CldrCaps cldr_caps_of(int geom, int GD, int GT) {
+    const CldrGeomDims& d = CLDR_GEOMS[geom];
+    return CldrCaps{d.NW * d.MA, d.NW * d.MQ, d.NW * d.MP, GD, GT};
+}
+
 struct CldrTiles {
     CldrCaps caps{};
     int NT = 0;

@@ -13,6 +13,8 @@
 
 #include "common.h"
 #include "cldr_tiles.h"
+#include "tile_meta.h"
+#include "stream_keys.h"
 #include "stream_kernels.h"
 #include "lds_args.h"
 #include "lds_plan.h"
@@ -120,6 +122,8 @@ struct Engine : EngineBase {
     std::vector<float*> lds_ring_extra;
     int64_t lds_instance = -1;       // MGADMM_Q_LDS_INSTANCE: template arguments of the k_admm_lds instance of the last launch
     int lds_unit = -1;               // MGADMM_Q_LDS_UNIT: which compilation of the instances it came from (0 / 1 / 2 = k_admm_lds / _ps / _pp)
+    StreamKeyLog stream_keys;        // MGADMM_Q_STREAM_KEYS / _KEY0 + i: distinct k_rows / k_tile / k_cldr instances launched (stream_keys.h)
+    static constexpr bool IS_F64 = std::is_same<S, double>::value;
     int lds_chunk = LDS_MAXJ;   // MGADMM_LDS_CHUNK: ADMM iterations per k_admm_lds launch when the iteration count is fixed (1 .. LDS_MAXJ)
     hipStream_t st_side = nullptr;
     hipEvent_t ev_main[LDS_NBOUND] = {nullptr}, ev_side[LDS_NBOUND] = {nullptr};
@@ -219,45 +223,11 @@ struct Engine : EngineBase {
             HostCsr A;
             if (g->has_perm) mg_permute_csr(src, g->perm, g->iperm, A);
             else A = src;
-            const int ntile = (N + R - 1) / R;
-            std::vector<int> tc((size_t)N * TILE_GW), hr(N + 1, 0), hcol, halo((size_t)ntile * TILE_HMAX, -1);
-            std::vector<float> tw((size_t)N * TILE_GW, 0.f), hval;
-            for (int tl = 0; tl < ntile; ++tl) {
-                const int lo = tl * R, hi = std::min(N, lo + R);
-                // halo list of the tile: out-of-tile columns in order of first use, at most TILE_HMAX
-                std::vector<int> hl;
-                auto halo_pos = [&](int c) -> int {
-                    for (size_t k = 0; k < hl.size(); ++k)
-                        if (hl[k] == c) return (int)k;
-                    if ((int)hl.size() < TILE_HMAX) { hl.push_back(c); return (int)hl.size() - 1; }
-                    return -1;
-                };
-                for (int i = lo; i < hi; ++i) {
-                    int used = 0;
-                    for (int e = A.rowptr[i]; e < A.rowptr[i + 1]; ++e) {
-                        const int c = A.col[e];
-                        int local = -1;
-                        if (used < TILE_GW) {
-                            if (c >= lo && c < hi) local = c - lo;
-                            else {
-                                const int hp = halo_pos(c);
-                                if (hp >= 0) local = R + hp;
-                            }
-                        }
-                        if (local >= 0) {
-                            tc[(size_t)i * TILE_GW + used] = local;
-                            tw[(size_t)i * TILE_GW + used] = A.val[e];
-                            ++used;
-                        } else {
-                            hcol.push_back(c);
-                            hval.push_back(A.val[e]);
-                        }
-                    }
-                    for (; used < TILE_GW; ++used) tc[(size_t)i * TILE_GW + used] = i - lo;
-                    hr[i + 1] = (int)hcol.size();
-                }
-                for (size_t k = 0; k < hl.size(); ++k) halo[(size_t)tl * TILE_HMAX + k] = hl[k];
-            }
+            TileMetaHost tm;
+            build_tile_meta(A, N, R, TILE_GW, tm);      // (tile_meta.h: plain C++, replayed on the CPU by tests/cpu/tile_meta_check.cpp)
+            const int ntile = tm.ntile;
+            const std::vector<int>&tc = tm.tl_col, &hr = tm.h_rowptr, &hcol = tm.h_col, &halo = tm.halo;
+            const std::vector<float>&tw = tm.tl_w, &hval = tm.h_val;
             if (getenv("MGADMM_TILE_STATS")) {           // diagnostics: how well the tile geometry fits the graph
                 long hsum = 0; int hfull = 0;
                 for (int tl = 0; tl < ntile; ++tl) {
@@ -267,15 +237,13 @@ struct Engine : EngineBase {
                 }
                 fprintf(stderr, "[mgadmm] tile_meta matrix %d: R=%d GW=%d tiles=%d  halo rows/tile mean %.2f (capacity %d, full tiles %d)  "
                                 "entries %d, overflow entries %zu (%.2f %%)\n", which, R, TILE_GW, ntile, (double)hsum / ntile, TILE_HMAX,
-                        hfull, A.nnz(), hcol.size(), 100.0 * hcol.size() / std::max(1, A.nnz()));
+                        hfull, A.nnz(), (size_t)tm.overflow(), 100.0 * tm.overflow() / std::max(1, A.nnz()));
             }
             MG_HIP(hipStreamSynchronize(st));
             auto fr = [](void* q) { if (q) (void)hipFree(q); };
             fr(d.tl_col); fr(d.tl_w); fr(d.halo); fr(d.h_rowptr); fr(d.h_col); fr(d.h_val);
             d = TileMetaDev();
-            const size_t nh = hcol.size() + 8;
-            hcol.resize(nh, 0);
-            hval.resize(nh, 0.f);
+            const size_t nh = hcol.size();      // (with the padding)
             MG_HIP(hipMalloc(&d.tl_col, tc.size() * sizeof(int)));
             MG_HIP(hipMalloc(&d.tl_w, tw.size() * sizeof(float)));
             MG_HIP(hipMalloc(&d.halo, halo.size() * sizeof(int)));
@@ -303,10 +271,13 @@ struct Engine : EngineBase {
     // measured on cfg3 (N = 10 000, B = 512), SpMM + LHS launch / with the folded vector update:
     //   geometry 1  380 us / 644 us      geometry 2  700 us / -      (a 16 / 32 / 48-row geometry 0 of 80 KiB ran 365 us / 711 us and
     //   spilled 52 VGPRs in the folded form: removed in round 3)
-    typedef ClG<4, 8, 2, 4, 5, 4> ClG1;     // 16 / 32 / 40 rows of 256 columns: 72 KiB (float), two workgroups per CU   (default)
-    typedef ClG<1, 8, 8, 11, 15, sizeof(S) == 4 ? 4 : 2> ClG2;   // 64 / 88 / 120 rows of 64 columns: 52 KiB (float) / 104 KiB (double); float: 128 VGPRs (6 waves per SIMD = 80 VGPRs spilled 87-100 of them in the folded form)
-    typedef ClG<2, 8, 4, 8, 10, 4> ClG3;    // 32 / 64 / 80 rows of 128 columns: 72 KiB (float): twice the rows per tile, a smaller halo share
-    typedef ClG<4, 16, 2, 3, 4, 4> ClG4;    // 32 / 48 / 64 rows of 256 columns, 16 waves: 112 KiB (float), one workgroup per CU
+    // (the numbers live in cldr_tiles.h, CLDR_GEOMS: the CPU replay of the tile builder reads the same table)
+    template <int I, int MINW_>
+    using ClGOf = ClG<CLDR_GEOMS[I].VECT, CLDR_GEOMS[I].NW, CLDR_GEOMS[I].MA, CLDR_GEOMS[I].MQ, CLDR_GEOMS[I].MP, MINW_>;
+    typedef ClGOf<1, 4> ClG1;     // 16 / 32 / 40 rows of 256 columns: 72 KiB (float), two workgroups per CU   (default)
+    typedef ClGOf<2, sizeof(S) == 4 ? 4 : 2> ClG2;   // 64 / 88 / 120 rows of 64 columns: 52 KiB (float) / 104 KiB (double); float: 128 VGPRs (6 waves per SIMD = 80 VGPRs spilled 87-100 of them in the folded form)
+    typedef ClGOf<3, 4> ClG3;    // 32 / 64 / 80 rows of 128 columns: 72 KiB (float): twice the rows per tile, a smaller halo share
+    typedef ClGOf<4, 4> ClG4;    // 32 / 48 / 64 rows of 256 columns, 16 waves: 112 KiB (float), one workgroup per CU
     // W_d^T slots per row: 12, or 16 / 24 when a row is longer (round 3: the PEMS-like graphs of 600 ... 2000 nodes have rows of 13 and
     // 14 entries and fell back to the two-pass path; the 16-slot instance is 5 % slower on graphs that do not need it).
     // W_d slots: 6 (no test at all) when no row is longer, else 8
@@ -383,13 +354,13 @@ struct Engine : EngineBase {
         cg.lds_bytes = (int)((size_t)nw * (mp + mq) * 64 * vect * sizeof(S));
         return cg;
     }
-    // the fused kernel needs Bp to be a multiple of its own chunk width
-    bool cldr_fits(const Geom& q) {
-        if (!cldr_usable()) return false;
+    // the fused kernel needs Bp to be a multiple of its own chunk width (float64: chunks of at most 128 columns)
+    bool cldr_width_fits(const Geom& q) const {
         int vect, nw, ma, mq, mp;
         cl_dims(vect, nw, ma, mq, mp);
         return q.Bp % (64 * vect) == 0 && (sizeof(S) == 4 || vect <= 2);
     }
+    bool cldr_fits(const Geom& q) { return cldr_usable() && cldr_width_fits(q); }
     template <class G, template <typename, int> class E, template <typename, int> class SRC, class... A>
     int rows_cldr_g(const Geom& q, const SRC<S, G::VECT>& src, const int* live, A... a) {
         if (cl_gt == 12) return cl_gd == 6 ? rows_cldr_gd<G, 6, 12, E, SRC>(q, src, live, a...) : rows_cldr_gd<G, 8, 12, E, SRC>(q, src, live, a...);
@@ -403,6 +374,7 @@ struct Engine : EngineBase {
         typedef E<S, G::VECT> Epi;
         auto fn = k_cldr<S, G::VECT, Epi, SRC<S, G::VECT>, G::NW, G::MA, G::MQ, G::MP, GD, GT, G::MINW>;
         MG_TRY(allow_dynamic_lds((const void*)fn, 150 * 1024));
+        stream_keys.note(stream_key(STREAM_K_CLDR, IS_F64, G::VECT, Epi::ID, SRC<S, G::VECT>::FOLD, G::NW, G::MA, G::MQ, G::MP, GD, GT, G::MINW));
         hipLaunchKernelGGL(fn, dim3(cg.grid), dim3(G::NW * 64), cg.lds_bytes, st, cg, mm, src, Epi{a...}, partials, live);
         cur_P = cg.P;
         return MGADMM_OK;
@@ -822,7 +794,9 @@ struct Engine : EngineBase {
             case MGADMM_Q_LDS_SLOTS: *out = lds.slots; break;
             case MGADMM_Q_LDS_CHUNK: *out = std::max(1, std::min(lds_chunk, LDS_MAXJ)); break;
             case MGADMM_Q_LDS_ROWS: *out = lds.NR; break;
-            case MGADMM_Q_CLDR_SLOTS: *out = cldr_dev.state == 1 ? cl_gt : 0; break;      // (prepared by the first operator application)
+            // (tables prepared by the first operator application; 0 as well when they exist but the batch the solver was created
+            // for is no multiple of the kernel's chunk width: the two-pass form runs)
+            case MGADMM_Q_CLDR_SLOTS: *out = cldr_dev.state == 1 && cldr_width_fits(make_geom(Bmax)) ? cl_gt : 0; break;
             case MGADMM_Q_LDS_INSTANCE: *out = lds_instance; break;
             case MGADMM_Q_LDS_UNIT: *out = lds_unit; break;
             case MGADMM_Q_LDS_CG_BARRIERS: *out = lds.ok ? lds.cg_barriers : 0; break;
@@ -834,7 +808,18 @@ struct Engine : EngineBase {
                 *out = make_tile_geom(make_geom(Bmax), tg) ? tg.R : 0;
                 break;
             }
-            default: mg_set_error("solver_query: unknown item %d", what); return MGADMM_ERR_INVALID;
+            case MGADMM_Q_STREAM_KEYS: *out = (int64_t)stream_keys.keys.size(); break;
+            default:
+                if (what >= MGADMM_Q_STREAM_KEY0 && (size_t)(what - MGADMM_Q_STREAM_KEY0) < stream_keys.keys.size()) {
+                    *out = stream_keys.keys[what - MGADMM_Q_STREAM_KEY0];
+                    break;
+                }
+                if (what >= MGADMM_Q_STREAM_KEY0) {
+                    mg_set_error("solver_query: stream key %d of %zu", what - MGADMM_Q_STREAM_KEY0, stream_keys.keys.size());
+                    return MGADMM_ERR_INVALID;
+                }
+                mg_set_error("solver_query: unknown item %d", what);
+                return MGADMM_ERR_INVALID;
         }
         return MGADMM_OK;
     }
@@ -936,6 +921,7 @@ struct Engine : EngineBase {
     int launch_tile2(const TileGeom& tg, const OpDesc& op, const TileMeta& tmv, const S* in, const Epi& epi, const int* live) {
         auto fn = k_tile<S, VEC, Epi, TGW, MR>;
         MG_TRY(allow_dynamic_lds((const void*)fn, 80 * 1024));
+        stream_keys.note(stream_key(STREAM_K_TILE, IS_F64, VEC, Epi::ID, false, TGW, MR));
         hipLaunchKernelGGL(fn, dim3(tg.grid), dim3(256), tg.lds_bytes, st, tg, op, tmv.tl_col, tmv.tl_w, tmv.halo, tmv.h_rowptr,
                            tmv.h_col, tmv.h_val, in, epi, partials, live, TileSrcPlain<S, VEC>());
         return MGADMM_OK;
@@ -963,6 +949,7 @@ struct Engine : EngineBase {
         MG_TRY(tile_meta(0, tg.R, 4, tmv));
         auto fn = k_tile<S, VEC, Epi, 4, 2, Src>;
         MG_TRY(allow_dynamic_lds((const void*)fn, 80 * 1024));
+        stream_keys.note(stream_key(STREAM_K_TILE, IS_F64, VEC, Epi::ID, true, 4, 2));
         hipLaunchKernelGGL(fn, dim3(tg.grid), dim3(256), tg.lds_bytes, st, tg, op, tmv.tl_col, tmv.tl_w, tmv.halo, tmv.h_rowptr,
                            tmv.h_col, tmv.h_val, r, Epi{a...}, partials, live, Src{p_old, p_new, x, d_alpha, d_beta});
         cur_P = tg.P;
@@ -994,6 +981,7 @@ struct Engine : EngineBase {
                 cur_P = tg.P;
             }
         } else {
+            stream_keys.note(stream_key(STREAM_K_ROWS, IS_F64, VEC, Epi::ID, false, GW));
             hipLaunchKernelGGL((k_rows<S, VEC, Epi, GW>), dim3(q.grid), dim3(256), 0, st, q, op, op.rowptr, op.col, op.val,
                                op.band_w, in, epi, partials, live);
             cur_P = q.P;

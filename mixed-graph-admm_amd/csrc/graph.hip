@@ -189,21 +189,7 @@ int mg_cluster_order(const HostCsr& A, const HostCsr* B, int csize, std::vector<
 }
 
 int mg_permute_csr(const HostCsr& A, const std::vector<int>& perm, const std::vector<int>& iperm, HostCsr& out) {
-    const int n = A.n;
-    out.n = n;
-    out.rowptr.assign(n + 1, 0);
-    out.col.clear();
-    out.val.clear();
-    out.col.reserve(A.nnz());
-    out.val.reserve(A.nnz());
-    for (int i = 0; i < n; ++i) {
-        int src = perm[i];
-        for (int e = A.rowptr[src]; e < A.rowptr[src + 1]; ++e) {
-            out.col.push_back(iperm[A.col[e]]);
-            out.val.push_back(A.val[e]);
-        }
-        out.rowptr[i + 1] = (int)out.col.size();
-    }
+    permute_csr(A, perm, iperm, out);      // (host_csr.h: plain C++, shared with the CPU replays of the tile builders)
     return MGADMM_OK;
 }
 

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "tile_meta.h"
 
 template <typename S, int V>
 struct alignas(sizeof(S) * V) Vec {
@@ -371,7 +372,7 @@ struct TileGeom {
 };
 constexpr int TILE_MAXR = 8;    // rows per wave and time step (4 waves -> R <= 32)
 constexpr int TILE_GW_MAX = 8;  // neighbour slots per row held in VGPR lanes: 4 (W_u), 6 (W_d) or 8 (W_d^T); MAXR*GW <= 64
-constexpr int TILE_HMAX = 20;   // halo rows (out-of-tile neighbours) staged in LDS per tile and step
+// TILE_HMAX (tile_meta.h): halo rows (out-of-tile neighbours) staged in LDS per tile and step
 constexpr int TILE_HPW = TILE_HMAX / 4;   // halo rows loaded by one wave
 
 // Per-(matrix, R) metadata built on the host (Engine::tile_meta):
@@ -1092,6 +1093,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_cldr(CldrGeom g, CldrMeta m, 
 // ------------------------------------------------------------------ epilogues
 template <typename S, int VEC>
 struct EpiStore {  // out = l
+    static constexpr int ID = 0;   // stream_keys.h
     static constexpr int NRED = 0;
     static constexpr bool HAS_PRE = false;
     S* out;
@@ -1104,6 +1106,7 @@ struct EpiStore {  // out = l
 // ADMM.py:349, 371-399).  p == nullptr: the gathered vector is p itself (Lu / diagonal case).
 template <typename S, int VEC>
 struct EpiLhs {
+    static constexpr int ID = 1;   // stream_keys.h
     static constexpr int NRED = 1;
     static constexpr bool HAS_PRE = true;   // the row of p can be requested ahead of time (time-innermost sweep)
     const S* p;
@@ -1147,6 +1150,7 @@ struct EpiLhs {
 // CG start: r = rhs - A x0 ; p = r ; x = x0 ; acc0 += r.r      (ADMM.py:339-347; `mask` only here, quirk Q2)
 template <typename S, int VEC>
 struct EpiCgInit {
+    static constexpr int ID = 2;   // stream_keys.h
     static constexpr int NRED = 1;
     static constexpr bool HAS_PRE = false;
     const S* x0;    // nullptr: the gathered vector is x0 itself
@@ -1189,6 +1193,7 @@ struct EpiCgInit {
 // still happens; frozen samples have alpha = beta = 0.
 template <typename S, int VEC>
 struct EpiCgUpdate {
+    static constexpr int ID = 3;   // stream_keys.h
     static constexpr bool ELEMENTWISE = true;   // never launched with a spatial operator
     static constexpr int NRED = 1;
     static constexpr bool HAS_PRE = false;
@@ -1215,6 +1220,7 @@ struct EpiCgUpdate {
 
 template <typename S, int VEC>
 struct EpiPUpdate {
+    static constexpr int ID = 4;   // stream_keys.h
     static constexpr bool ELEMENTWISE = true;   // never launched with a spatial operator
     static constexpr int NRED = 0;
     static constexpr bool HAS_PRE = false;
@@ -1247,6 +1253,7 @@ struct EpiPUpdate {
 // x += alpha p (ADMM.py:352) for the LAST iteration of a CG solve whose p-updates are folded into the SpMM kernel
 template <typename S, int VEC>
 struct EpiXFinal {
+    static constexpr int ID = 5;   // stream_keys.h
     static constexpr bool ELEMENTWISE = true;
     static constexpr int NRED = 0;
     static constexpr bool HAS_PRE = false;
@@ -1271,6 +1278,7 @@ struct EpiXFinal {
 // out = a*in + b*w     (gamma + rho*phi ; gamma_u/2 + rho_u/2 x : ADMM.py:559, 579, 587)
 template <typename S, int VEC>
 struct EpiLin2 {
+    static constexpr int ID = 6;   // stream_keys.h
     static constexpr bool ELEMENTWISE = true;   // never launched with a spatial operator
     static constexpr int NRED = 0;
     static constexpr bool HAS_PRE = false;
@@ -1292,6 +1300,7 @@ struct EpiLin2 {
 // RHS_x = [Ldr^T(gamma + rho phi)]/2 + (rho_u zu + rho_d zd)/2 - (gamma_u + gamma_d)/2 + Hty   (ADMM.py:556-564)
 template <typename S, int VEC>
 struct EpiRhsX {
+    static constexpr int ID = 7;   // stream_keys.h
     static constexpr int NRED = 0;
     static constexpr bool HAS_PRE = false;
     const S *zu, *zd, *gu, *gd, *y;
@@ -1324,6 +1333,7 @@ struct EpiRhsX {
 // acc: 0 ||x-x_old||^2, 1 ||x-zu||^2, 2 ||zu-zu_old||^2, 3 ||x-zd||^2, 4 ||zd-zd_old||^2, 5 ||Hx-y||^2
 template <typename S, int VEC>
 struct EpiDual {
+    static constexpr int ID = 8;   // stream_keys.h
     static constexpr bool ELEMENTWISE = true;   // never launched with a spatial operator
     static constexpr int NRED = 6;
     static constexpr bool HAS_PRE = false;
@@ -1384,6 +1394,7 @@ __device__ __forceinline__ S soft_thr(S s, S thr) {
 // ||phi - Ldr x||^2, ||phi - phi_old||^2, ||Ldr x||_1 and sum (Ldr x)^2.  update == 0: metrics only.
 template <typename S, int VEC>
 struct EpiPhi {
+    static constexpr int ID = 9;   // stream_keys.h
     static constexpr int NRED = 4;
     static constexpr bool HAS_PRE = false;
     const S* phi_old;
@@ -1418,6 +1429,7 @@ struct EpiPhi {
 // stand-alone phi_direct(x, gamma)  (ADMM.py:401-408)
 template <typename S, int VEC>
 struct EpiPhiDirect {
+    static constexpr int ID = 10;   // stream_keys.h
     static constexpr int NRED = 0;
     static constexpr bool HAS_PRE = false;
     const S* gamma;
@@ -1436,6 +1448,7 @@ struct EpiPhiDirect {
 // GLR: acc0 += x . Lu x     (ADMM.py:245-246)
 template <typename S, int VEC>
 struct EpiDot {
+    static constexpr int ID = 11;   // stream_keys.h
     static constexpr int NRED = 1;
     static constexpr bool HAS_PRE = false;
     __device__ void begin(int) {}
@@ -1595,6 +1608,7 @@ static __global__ void k_cg_batchmax_iters(const int* __restrict__ n_active, int
 // apply_op_Ln on the line graph (ADMM.py:253-261): y[t] = x[t] - x[t+1]/sqrt(2) for t < T-1, y[T-1] = x[T-1] - x[T-2]/sqrt(2)
 template <typename S, int VEC>
 struct EpiLnLine {
+    static constexpr int ID = 12;   // stream_keys.h
     static constexpr bool ELEMENTWISE = true;
     static constexpr int NRED = 0;
     static constexpr bool HAS_PRE = false;
@@ -1615,6 +1629,7 @@ struct EpiLnLine {
 // out = add + l
 template <typename S, int VEC>
 struct EpiAddTo {
+    static constexpr int ID = 13;   // stream_keys.h
     static constexpr int NRED = 0;
     static constexpr bool HAS_PRE = false;
     const S* add;

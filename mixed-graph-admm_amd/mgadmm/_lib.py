@@ -31,6 +31,7 @@ NPROF = 4
 (Q_LDS_OK, Q_LDS_TPG, Q_LDS_THREADS, Q_LDS_BYTES, Q_LDS_ROW_STRIDE, Q_NNZ_U, Q_NNZ_D, Q_NNZ_DT, Q_TILE_ROWS, Q_LDS_UNIFORM,
  Q_LDS_TAIL_PAIRS, Q_LDS_LEAD, Q_LDS_SLOTS, Q_LDS_CHUNK, Q_LDS_ROWS, Q_CLDR_SLOTS, Q_LDS_INSTANCE, Q_LDS_CG_BARRIERS,
  Q_LDS_UNIT) = range(19)
+Q_STREAM_KEYS, Q_STREAM_KEY0 = 19, 1000
 LDS_UNITS = ("k_admm_lds", "k_admm_lds_ps", "k_admm_lds_pp")      # values of Q_LDS_UNIT (-1: no LDS launch yet)
 
 _i32p = C.POINTER(C.c_int32)
@@ -173,3 +174,36 @@ def decode_lds_instance(v):
 def lds_instance(handle):
     """Name of the k_admm_lds instance the solver's last LDS launch ran (None before the first launch)."""
     return decode_lds_instance(query(handle, Q_LDS_INSTANCE))
+
+
+# csrc/stream_keys.h: epilogue functors by ID, and the integer template arguments that follow the functor(s) per kernel
+STREAM_EPILOGUES = ("EpiStore", "EpiLhs", "EpiCgInit", "EpiCgUpdate", "EpiPUpdate", "EpiXFinal", "EpiLin2", "EpiRhsX", "EpiDual",
+                    "EpiPhi", "EpiPhiDirect", "EpiDot", "EpiLnLine", "EpiAddTo")
+STREAM_KERNELS = ("k_rows", "k_tile", "k_cldr")
+_STREAM_NARGS = (1, 2, 7)
+
+
+def decode_stream_key(v):
+    """Packed MGADMM_Q_STREAM_KEY0 + i value -> the instance name as `nm -C` prints it, e.g.
+    'k_tile<float, 4, EpiLhs<float, 4>, 4, 2, TileSrcFold<float, 4> >' or
+    'k_cldr<double, 1, EpiStore<double, 1>, CldrSrcPlain<double, 1>, 8, 8, 11, 15, 6, 12, 2>'."""
+    kern, s, vec = v & 3, "double" if (v >> 2) & 1 else "float", (v >> 3) & 7
+    epi, fold = STREAM_EPILOGUES[(v >> 6) & 31], (v >> 11) & 1
+    args = [str((v >> (12 + 6 * i)) & 63) for i in range(_STREAM_NARGS[kern])]
+    e = f"{epi}<{s}, {vec}>"
+    src = f"{'Fold' if fold else 'Plain'}<{s}, {vec}>"
+    if kern == 0:
+        assert not fold
+        return f"k_rows<{s}, {vec}, {e}, {args[0]}>"
+    if kern == 1:
+        return f"k_tile<{s}, {vec}, {e}, {args[0]}, {args[1]}, TileSrc{src} >"
+    return f"k_cldr<{s}, {vec}, {e}, CldrSrc{src}, " + ", ".join(args) + ">"
+
+
+def stream_keys(handle):
+    return [query(handle, Q_STREAM_KEY0 + i) for i in range(query(handle, Q_STREAM_KEYS))]
+
+
+def stream_instances(handle):
+    """Names of the distinct k_rows / k_tile / k_cldr instances the solver has launched since it was created."""
+    return {decode_stream_key(v) for v in stream_keys(handle)}
