@@ -152,6 +152,18 @@ def main():
     for i, f in enumerate(factors):
         print(f"  {f:>14.3g} " + "".join(f"{n_it[i * 3 + j].mean():>9.1f}" for j in range(3)))
 
+    # the solver chooses the penalties itself: residual balancing per sample on the device, a step after every 4th iteration
+    # (between two kernel launches; no host round trip).  rho_history: (periods, 3, B) = rho, rho_u, rho_d by period
+    blk._reset_history()
+    blk.admm_convergence = "per_sample"
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    blk.solve(y[:nw], return_state=False, adaptive_rho={"every": 4, "mu": 10, "tau": 2})
+    torch.cuda.synchronize(); dt = time.perf_counter() - t0
+    blk.admm_convergence = "whole_batch"
+    print(f"adaptive penalties: {nw} windows in {dt * 1e3:.1f} ms, {np.asarray(blk.n_iters_per_sample).mean():.1f} ADMM iterations on average; "
+          f"rho, rho_u, rho_d of window 0 at the end: " + ", ".join(f"{v:.3g}" for v in blk.rho_final[:, 0])
+          + f" (start: {admm_info['rho']:.3g}, {admm_info['rho_u']:.3g}, {admm_info['rho_d']:.3g})")
+
     ix, iy, mask = ds.get_interpolated_batch(starts, 0.4)
     blk._reset_history()
     x_int = blk.combined_loop(iy, mask=mask, print_info=False)

@@ -158,7 +158,8 @@ typedef struct mgadmm_solver mgadmm_solver;
  * mgadmm_params gained cg_convergence and max_inner_iter; 0.3: mgadmm_params gained admm_convergence, mgadmm_history gained
  * n_iters_per_sample): a caller built against an older header must be rebuilt -- compare the string before passing structs.
  * The patch number counts additions that leave every struct alone (0.3.1: mgadmm_solver_set_sample_params;
- * 0.3.2: mgadmm_solver_set_sample_graphs; 0.3.3: mgadmm_solver_set_param_schedule). */
+ * 0.3.2: mgadmm_solver_set_sample_graphs; 0.3.3: mgadmm_solver_set_param_schedule;
+ * 0.3.4: mgadmm_solver_set_adaptive_rho, mgadmm_solver_get_adaptive_history). */
 const char* mgadmm_version(void);
 const char* mgadmm_last_error(void);
 
@@ -244,6 +245,37 @@ typedef struct {
  * mgadmm_two_loops and the fine-grained entry points (mgadmm_lhs, mgadmm_cg, mgadmm_phi_direct, mgadmm_apply) IGNORE the
  * schedule: they keep using the scalars of mgadmm_params. */
 int mgadmm_solver_set_param_schedule(mgadmm_solver* s, const mgadmm_param_schedule* sch, int32_t n_rows, int32_t B, int32_t first_row);
+/* Adaptive penalties: residual balancing (Boyd et al., Distributed Optimization and Statistical Learning via ADMM, 3.4.1) of
+ * rho, rho_u and rho_d, per sample, on the device.  After every `every`-th iteration (counted from `start`, the iterations the
+ * problem has run in earlier calls: start % every == 0) each running sample compares, per pair (PRI_ZU, DUAL_ZU) -> rho_u,
+ * (PRI_PHI, DUAL_PHI) -> rho, (PRI_ZD, DUAL_ZD) -> rho_d of that iteration's sums of metrics_per_sample, with its current
+ * penalty r:  s2 = r * r * dual2;  pri2 > mu^2 s2: r = min(r * tau, rho_max);  s2 > mu^2 pri2: r = max(r * (1 / tau), rho_min).
+ * Doubles, multiplications and comparisons only; a pair the ablation does not iterate on is left alone.  The dual residuals
+ * of the history are unscaled (ADMM.py:618-636), hence the factor r; for phi, r ||phi - phi_old|| stands for
+ * r ||Ldr^T (phi - phi_old)||.  No step follows iteration count `until` (0: no limit).  The start values are the table of
+ * mgadmm_solver_set_sample_params where one is set, otherwise the scalars.  rho_min / rho_max: in the order rho, rho_u, rho_d. */
+typedef struct {
+    int32_t every, until;
+    double mu, tau;
+    double rho_min[3], rho_max[3];
+} mgadmm_adaptive_rho;
+/* For the following mgadmm_solve / mgadmm_solve_from calls; ar == NULL clears.  every outside [1, 16], mu <= 1, tau <= 1,
+ * rho_min <= 0 or > rho_max, until < 0, start < 0 or no multiple of every -> MGADMM_ERR_INVALID (the message names the
+ * parameter).  While it is set (decided when a solve starts, before anything runs; the messages contain "adaptive_rho"):
+ *   - LDS-resident float32 path only (MGADMM_PATH_STREAM, MGADMM_F64, MGADMM_CG_BATCH_MAX, a graph the LDS path cannot hold
+ *     -> MGADMM_ERR_UNSUPPORTED); the launches take the kernels k_admm_lds_pp (MGADMM_Q_LDS_UNIT = 2) and run the largest
+ *     number of iterations <= MGADMM_Q_LDS_CHUNK that divides `every`; a small kernel between two launches applies the step;
+ *   - check_stop = 1 with MGADMM_ADMM_WHOLE_BATCH, or a param_schedule set at the same time -> MGADMM_ERR_UNSUPPORTED;
+ *     a B other than the sample_params table's -> MGADMM_ERR_INVALID;
+ *   - it combines with mgadmm_solver_set_sample_params, mgadmm_solver_set_sample_graphs and the per-sample stop.
+ * A solve equals, bit for bit, the chain of solves of `every` iterations by mgadmm_solve_from with the rule applied to
+ * metrics_per_sample on the host and the penalties set as scalars.  mgadmm_two_loops and the fine-grained entry points IGNORE it. */
+int mgadmm_solver_set_adaptive_rho(mgadmm_solver* s, const mgadmm_adaptive_rho* ar, int32_t start);
+/* The penalties of the last solve: *n_periods = 1 + the steps it took (0: it did not adapt); rho_hist (or NULL) receives
+ * min(max_periods, *n_periods) rows [3][B]: rho, rho_u, rho_d in force during period p -- row 0 the start values, row p the
+ * values after step p (the last row of a solve that ends on a step is what a resumed solve starts with).  NaN past a
+ * sample's own stop (per-sample stop).  Another B than the solve's -> MGADMM_ERR_INVALID. */
+int mgadmm_solver_get_adaptive_history(mgadmm_solver* s, int32_t B, double* rho_hist, int32_t max_periods, int32_t* n_periods);
 /* bytes of device workspace held by the solver */
 int64_t mgadmm_solver_workspace_bytes(const mgadmm_solver* s);
 /* which path (MGADMM_PATH_STREAM / MGADMM_PATH_LDS) a batch of size B would take */

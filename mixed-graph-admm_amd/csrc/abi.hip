@@ -61,6 +61,16 @@ int mgadmm_solver_set_param_schedule(mgadmm_solver* s, const mgadmm_param_schedu
     return s->eng->set_param_schedule(sch, n_rows, B, first_row);
 }
 
+int mgadmm_solver_set_adaptive_rho(mgadmm_solver* s, const mgadmm_adaptive_rho* ar, int32_t start) {
+    MG_REQUIRE(s, "set_adaptive_rho: null solver");
+    return s->eng->set_adaptive_rho(ar, start);
+}
+
+int mgadmm_solver_get_adaptive_history(mgadmm_solver* s, int32_t B, double* rho_hist, int32_t max_periods, int32_t* n_periods) {
+    MG_REQUIRE(s, "get_adaptive_history: null solver");
+    return s->eng->get_adaptive_history(B, rho_hist, max_periods, n_periods);
+}
+
 int64_t mgadmm_solver_workspace_bytes(const mgadmm_solver* s) { return s ? s->eng->workspace_bytes() : 0; }
 int mgadmm_solver_path(const mgadmm_solver* s, int32_t B) { return s ? s->eng->path_for(B) : MGADMM_ERR_INVALID; }
 

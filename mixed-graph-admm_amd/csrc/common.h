@@ -99,6 +99,8 @@ struct EngineBase {
     virtual int set_sample_params(const mgadmm_sample_params* sp, int B) = 0;
     virtual int set_sample_graphs(int n_sets, mgadmm_graph* const* graphs, const int32_t* set_of_sample, int B) = 0;
     virtual int set_param_schedule(const mgadmm_param_schedule* sch, int n_rows, int B, int first_row) = 0;
+    virtual int set_adaptive_rho(const mgadmm_adaptive_rho* ar, int start) = 0;
+    virtual int get_adaptive_history(int B, double* rho_hist, int max_periods, int* n_periods) = 0;
     virtual int64_t workspace_bytes() const = 0;
     virtual int path_for(int B) const = 0;
     virtual int query(int what, int64_t* out) const = 0;

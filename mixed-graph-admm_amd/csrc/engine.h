@@ -107,6 +107,16 @@ struct Engine : EngineBase {
     LdsSampleParams* d_sch = nullptr;
     size_t sch_elems = 0;
     int sch_up_B = 0;             // batch the device table was formed for; 0 = it has to be formed
+    // adaptive penalties (mgadmm_solver_set_adaptive_rho, lds_adapt.h): the parameters, and per solve the table of
+    // max_admm_iter x B records k_lds_adapt writes between the launches, the six weights of every sample as doubles and the
+    // history of the three penalties by period
+    bool ad_on = false;
+    ldsadapt::Params ad;
+    int ad_start = 0;
+    LdsSampleParams* d_ad_tab = nullptr;
+    double *d_ad_w = nullptr, *d_ad_hist = nullptr;
+    size_t ad_tab_elems = 0, ad_w_elems = 0, ad_hist_elems = 0;
+    int ad_last_B = 0, ad_last_periods = 0;   // of the last solve (mgadmm_solver_get_adaptive_history); 0 periods: it did not adapt
     // per-sample graph weights (mgadmm_solver_set_sample_graphs, lds_graph_sets.h): the images of the sets back to back and the
     // set of every sample; the solver's own image and the planner's switches are kept for the comparison with every set
     int sg_B = 0, sg_sets = 0;    // samples / sets of the table; sg_B = 0: none set
@@ -149,7 +159,7 @@ struct Engine : EngineBase {
         fr(vec_pool); fr(partials); fr(d_rr); fr(d_alpha); fr(d_beta); fr(d_alpha_hist); fr(d_beta_hist);
         fr(d_active); fr(d_iters_tmp); fr(d_nact); fr(d_nonfinite); fr(d_ps); fr(d_hist); fr(d_dxps);
         fr(d_dxpart); fr(d_hist_ps); fr(d_cg_iters); fr(d_lds_csr); fr(d_m2); fr(d_stop); fr(d_ps_ring); fr(d_pstop); fr(d_ps_full);
-        fr(d_sp); fr(d_sg_img); fr(d_sg_set); fr(d_sch);
+        fr(d_sp); fr(d_sg_img); fr(d_sg_set); fr(d_sch); fr(d_ad_tab); fr(d_ad_w); fr(d_ad_hist);
         for (float* b : lds_ring_extra) if (b) (void)hipFree(b);
         if (st_side) (void)hipStreamDestroy(st_side);
         for (auto& e : ev_main) if (e) (void)hipEventDestroy(e);
@@ -685,6 +695,64 @@ struct Engine : EngineBase {
         MG_TRY(grow(d_sch, sch_elems, rec.size()));
         MG_HIP(hipMemcpy(d_sch, rec.data(), sizeof(LdsSampleParams) * rec.size(), hipMemcpyHostToDevice));
         sch_up_B = B;
+        return MGADMM_OK;
+    }
+
+    // ---------------------------------------------------------------- adaptive penalties
+    // Residual balancing of rho, rho_u, rho_d per sample (lds_adapt.h) in the solves that follow; `start`: iterations the
+    // problem has run already (a resumed solve continues the periods).  nullptr clears
+    int set_adaptive_rho(const mgadmm_adaptive_rho* ar, int start) override {
+        if (ar == nullptr) {
+            ad_on = false;
+            return MGADMM_OK;
+        }
+        ldsadapt::Params q;
+        q.every = ar->every; q.until = ar->until; q.mu = ar->mu; q.tau = ar->tau;
+        q.tau_inv = 1.0 / ar->tau;
+        for (int f = 0; f < 3; ++f) { q.rho_min[f] = ar->rho_min[f]; q.rho_max[f] = ar->rho_max[f]; }
+        std::string why;
+        if (!ldsadapt::validate(q, start, why)) {
+            mg_set_error("set_adaptive_rho: %s", why.c_str());
+            return MGADMM_ERR_INVALID;
+        }
+        ad = q; ad_start = start; ad_on = true;
+        return MGADMM_OK;
+    }
+
+    // A solve with adaptive penalties set: decided when the solve starts, before anything is enqueued.  The step runs between
+    // launches of the LDS-resident kernel and writes the table only k_admm_lds_pp reads
+    int check_adaptive(int B) const {
+        const char* why = nullptr;
+        if (!std::is_same<S, float>::value) why = "float64 arithmetic runs on the streaming path";
+        else if (p.path == MGADMM_PATH_STREAM) why = "path is MGADMM_PATH_STREAM";
+        else if (p.cg_convergence == MGADMM_CG_BATCH_MAX) why = "cg_convergence batch_max runs on the streaming path";
+        else if (!lds.ok) why = "the LDS-resident path cannot hold this graph (it needs T*N*8 B + tables <= 160 KiB and N*G <= 1024)";
+        if (why) {
+            mg_set_error("solve: adaptive_rho (penalties adapted on the device) is implemented by the LDS-resident float32 path only: %s", why);
+            return MGADMM_ERR_UNSUPPORTED;
+        }
+        if (p.check_stop && p.admm_convergence == MGADMM_ADMM_WHOLE_BATCH) {
+            mg_set_error("solve: adaptive_rho with check_stop needs admm_convergence per_sample (every sample carries its own penalties: "
+                         "the whole_batch stop test would sum the residuals of different problems); or run a fixed count with check_stop = 0");
+            return MGADMM_ERR_UNSUPPORTED;
+        }
+        if (sch_rows > 0) {
+            mg_set_error("solve: adaptive_rho and a param_schedule are both set: the adaptation writes the table a schedule would fill");
+            return MGADMM_ERR_UNSUPPORTED;
+        }
+        MG_REQUIRE(sp_B == 0 || B == sp_B, "solve: adaptive_rho takes its start values from the sample_params table of %d samples, the solve has B = %d",
+                   sp_B, B);
+        return MGADMM_OK;
+    }
+
+    // the history of the last solve: rho_hist[p][3][B] = rho, rho_u, rho_d of period p (NaN past a sample's own stop)
+    int get_adaptive_history(int B, double* rho_hist, int max_periods, int* n_periods) override {
+        MG_REQUIRE(n_periods, "get_adaptive_history: n_periods is null");
+        *n_periods = ad_last_periods;
+        if (ad_last_periods == 0 || rho_hist == nullptr || max_periods <= 0) return MGADMM_OK;
+        MG_REQUIRE(B == ad_last_B, "get_adaptive_history: the last adaptive_rho solve had B = %d, not %d", ad_last_B, B);
+        MG_HIP(hipSetDevice(g->device));
+        MG_HIP(hipMemcpy(rho_hist, d_ad_hist, sizeof(double) * 3 * (size_t)B * std::min(max_periods, ad_last_periods), hipMemcpyDeviceToHost));
         return MGADMM_OK;
     }
 
@@ -1395,6 +1463,8 @@ struct Engine : EngineBase {
         MG_REQUIRE(y && x_out, "solve: null pointer");
         if (state_in) MG_TRY(check_state_in(x0, state_in));
         st = s;
+        ad_last_periods = 0;
+        if (ad_on) MG_TRY(check_adaptive(B));
         if (sp_B > 0) MG_TRY(check_sample_params(B));
         if (sg_B > 0) MG_TRY(check_sample_graphs(B));
         if (sch_rows > 0) MG_TRY(check_param_schedule(B));
@@ -1725,6 +1795,7 @@ struct Engine : EngineBase {
         float* xo;                        // the caller's x_out
         mgadmm_history* hist;
         int n_done = 0, rc = MGADMM_OK;
+        std::vector<int> ad_bounds;       // adaptive penalties: iterations done at every step enqueued so far
     };
 
     // buffer of an iterate slot; slots beyond the workspace vectors are allocated here
@@ -1843,6 +1914,46 @@ struct Engine : EngineBase {
         return MGADMM_OK;
     }
 
+    // Adaptive penalties, start of a solve: every row of the table holds the records of the start weights (the per-sample
+    // table where one is set, otherwise the scalars), period 0 of the history the start penalties, the later periods NaN
+    int adapt_begin(LdsRun& r) {
+        const int B = r.B, max_it = r.s.max_it;
+        const ldsparam::Source src = weight_source(false);
+        std::vector<LdsSampleParams> row, rec;
+        ldsparam::fill_records(src, p.ablation, B, row);      // (one row: no schedule)
+        rec.reserve((size_t)max_it * B);
+        for (int k = 0; k < max_it; ++k) rec.insert(rec.end(), row.begin(), row.end());
+        std::vector<double> w((size_t)ldsparam::NW * B);
+        for (int f = 0; f < ldsparam::NW; ++f)
+            for (int b = 0; b < B; ++b) w[(size_t)f * B + b] = ldsparam::weight_of(src, f, 0, b);
+        const size_t hist_rows = (size_t)max_it / ad.every + 2;
+        MG_TRY(grow(d_ad_tab, ad_tab_elems, rec.size()));
+        MG_TRY(grow(d_ad_w, ad_w_elems, w.size()));
+        MG_TRY(grow(d_ad_hist, ad_hist_elems, hist_rows * 3 * B));
+        MG_HIP(hipMemcpy(d_ad_tab, rec.data(), sizeof(LdsSampleParams) * rec.size(), hipMemcpyHostToDevice));
+        MG_HIP(hipMemcpy(d_ad_w, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice));
+        MG_HIP(hipMemcpy(d_ad_hist, w.data(), sizeof(double) * 3 * B, hipMemcpyHostToDevice));
+        MG_HIP(hipMemsetAsync(d_ad_hist + (size_t)3 * B, 0xFF, sizeof(double) * (hist_rows - 1) * 3 * B, st));      // (all bits set: a NaN)
+        r.a.sp = d_ad_tab;
+        r.a.sp_rows = max_it; r.a.sp_row0 = 0; r.a.sp_stride = B;
+        ad_last_B = B;
+        return MGADMM_OK;
+    }
+    // after the launch whose last iteration is `it`: the step, if one follows that iteration (ldsadapt::step_after), on the
+    // caller's stream; ps = the per-sample sums [NMETRIC][Bp] of iteration `it`
+    int adapt_step(LdsRun& r, int it, const double* ps) {
+        if (!ad_on || !ldsadapt::step_after(it, ad_start, ad.every, ad.until)) return MGADMM_OK;
+        const ldsadapt::Rows rows = ldsadapt::rows_after(it, ad_start, ad.every, ad.until, r.s.max_it);
+        r.ad_bounds.push_back(it + 1);
+        LdsAdaptArgs k;
+        k.ps = ps; k.pstop = r.a.pstop; k.w = d_ad_w; k.table = d_ad_tab;
+        k.hist = d_ad_hist + r.ad_bounds.size() * 3 * (size_t)r.B;
+        k.B = r.B; k.Bp = r.Bp; k.row_first = rows.first; k.row_last = rows.last;
+        k.ablation = p.ablation; k.has_phi = r.has_phi; k.has_zd = r.has_zd;
+        k.q = ad;
+        return mg_lds_adapt(k, st);
+    }
+
     // CHUNKS: one launch per chunk on the caller's stream; the whole-batch metrics of the chunk on the helper stream, ordered by
     // the events of lds_schedule.h (per-sample stop: one stream, no metrics, the host ends when every sample has stopped)
     int lds_run_chunks(LdsRun& r) {
@@ -1859,6 +1970,7 @@ struct Engine : EngineBase {
             if (r.s.per_sample) {
                 a.ps = d_ps_full + (size_t)ch.it0 * row;
                 MG_TRY(launch_lds(a, r.B));
+                MG_TRY(adapt_step(r, ch.it0 + ch.Jc - 1, a.ps + (size_t)(ch.Jc - 1) * row));      // (the sums of every iteration are kept)
                 r.n_done = ch.it0 + ch.Jc;
                 int stopped = 0;
                 MG_TRY(lagged_word(c, a.pstop_count, &stopped));
@@ -1870,6 +1982,10 @@ struct Engine : EngineBase {
             MG_TRY(launch_lds(a, r.B));
             MG_HIP(hipEventRecord(ev_main[ch.ev], st));
             MG_HIP(hipStreamWaitEvent(st_side, ev_main[ch.ev], 0));
+            // adaptive penalties: the step reads the last row of the chunk's metric set on `st`, in stream order before launch
+            // c + 1; the first launch that writes the set again is launch c + 3 on the same stream, so the hazard rule of
+            // lds_schedule.h holds as it stands (the metric kernels beside it only read the set)
+            MG_TRY(adapt_step(r, ch.it0 + ch.Jc - 1, a.ps + (size_t)(ch.Jc - 1) * row));
             for (int k = 0; k < ch.Jc; ++k) MG_TRY(lds_batch_metrics(r, ch.it0 + k, a.ps + (size_t)k * row, st_side));
             MG_HIP(hipEventRecord(ev_side[ch.ev], st_side));
             r.n_done = ch.it0 + ch.Jc;
@@ -1895,6 +2011,7 @@ struct Engine : EngineBase {
                 MG_TRY(fill((S*)d_beta_hist, 3 * K * r.Bp, (S)NAN));
             }
             MG_TRY(launch_lds(a, r.B));
+            MG_TRY(adapt_step(r, it, a.ps));
             if (!r.s.per_sample) MG_TRY(lds_batch_metrics(r, it, a.ps, st));
             if (r.record) {
                 for (int w = 0; w < 3; ++w) {
@@ -1964,7 +2081,8 @@ struct Engine : EngineBase {
             // costs one copy).  Outputs must not alias y / mask (mgadmm.h).
             r.xo = static_cast<float*>(x_out);
             r.s = ldssched::Schedule::pick(lds_async != 0, r.record, p.check_stop != 0, p.admm_convergence == MGADMM_ADMM_PER_SAMPLE,
-                                           lds_chunk, p.max_admm_iter);
+                                           ad_on ? ldsadapt::adapt_J(ad.every, std::max(1, std::min(lds_chunk, LDS_MAXJ))) : lds_chunk,
+                                           p.max_admm_iter);
             const ldssched::Schedule& s = r.s;
             const bool chunked = s.kind == ldssched::CHUNKS;
             MG_TRY(ensure_hist_ps(hist, B));
@@ -1997,9 +2115,12 @@ struct Engine : EngineBase {
                 r.a.sp = d_sch;
                 r.a.sp_rows = sch_rows; r.a.sp_row0 = sch_row0; r.a.sp_stride = B;
             }
+            if (ad_on) MG_TRY(adapt_begin(r));      // (check_adaptive) the table the steps between the launches write
             MG_TRY(chunked ? lds_run_chunks(r) : lds_run_steps(r));
             std::vector<int> nps;         // per-sample stop: iterations of every sample
             if (s.per_sample) MG_TRY(lds_finish_per_sample(r, nps));
+            if (ad_on)      // periods of the history: the start values and the steps that followed an iteration some sample ran
+                ad_last_periods = 1 + (int)std::count_if(r.ad_bounds.begin(), r.ad_bounds.end(), [&](int n) { return n <= r.n_done; });
             // (per-sample stop: a stopped sample stored x_out[b] itself, the others ran max_it iterations and their last iterate is x_out)
             float* const xc = s.per_sample ? r.xo : lds_xbuf(r, r.n_done);
             if (xc != r.xo)       // early stop on another buffer

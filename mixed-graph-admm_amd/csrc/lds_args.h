@@ -4,6 +4,7 @@
 
 #include "lds_consts.h"     // LDS_NLEAD, LDS_MAXJ, lds_instance_key
 #include "lds_param_table.h"   // LdsSampleParams, sched_row
+#include "lds_adapt.h"         // ldsadapt::Params
 
 // scalar part of the launch arguments: a trip of the loop inside k_admm_lds reads it from the kernarg segment
 struct LdsArgsCore {
@@ -113,3 +114,17 @@ int mg_lds_ps_history(const double* ps, const int* pstop, int n_it, int max_it, 
 // stop test of one ADMM iteration on the device (ADMM.py:645-646 + the NaN asserts): *stop = it + 1 when both residual maxima
 // are below tol, -(it + 1) when a metric or the iterate is not finite; leaves a stop word that is already set alone
 int mg_lds_stop_test(const double* metrics_row, const int* nonfinite, int has_phi, int has_zd, double tol, int it, int* stop, hipStream_t st);
+// One adaptation step of the penalties (lds_adapt.h), one thread per sample, between two launches of k_admm_lds_pp on the same
+// stream.  A sample whose stop word is set is left alone; every other sample balances its three penalties on the six residual
+// sums of the period's last iteration, keeps them in `w`, writes its records of rows [row_first, row_last) of the weight table
+// through ldsparam::record_of and appends the penalties to the history.  Plain vector stores only
+struct LdsAdaptArgs {
+    const double* ps;          // [NMETRIC][Bp] per-sample sums of the period's last iteration
+    const int* pstop;          // [Bp] per-sample stop words, or nullptr
+    double* w;                 // [6][B] the six weights of every sample, as doubles (the three mus never change)
+    LdsSampleParams* table;    // [rows][B] records, row = iteration of the solve
+    double* hist;              // [3][B] row of the history this step appends
+    int B, Bp, row_first, row_last, ablation, has_phi, has_zd;
+    ldsadapt::Params q;
+};
+int mg_lds_adapt(const LdsAdaptArgs& a, hipStream_t st);

@@ -50,3 +50,26 @@ int mg_lds_ps_history(const double* ps, const int* pstop, int n_it, int max_it, 
     MG_HIP(hipGetLastError());
     return MGADMM_OK;
 }
+
+__global__ __launch_bounds__(256) void k_lds_adapt(const LdsAdaptArgs a) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= a.B) return;
+    if (a.pstop != nullptr && a.pstop[b] != 0) return;      // a stopped sample keeps its history NaN from here on
+    static_assert(MGADMM_M_DUAL_ZD == MGADMM_M_PRI_ZU + 5, "the six residual sums are consecutive metrics");
+    double res[6], w[ldsparam::NW];
+    for (int k = 0; k < 6; ++k) res[k] = a.ps[(size_t)(MGADMM_M_PRI_ZU + k) * a.Bp + b];
+    for (int f = 0; f < ldsparam::NW; ++f) w[f] = a.w[(size_t)f * a.B + b];
+    ldsadapt::step(w, res, a.has_phi, a.has_zd, a.q);
+    for (int f = 0; f < 3; ++f) {
+        a.w[(size_t)f * a.B + b] = w[f];
+        a.hist[(size_t)f * a.B + b] = w[f];
+    }
+    const LdsSampleParams rec = ldsparam::record_of(a.ablation, w);
+    for (int row = a.row_first; row < a.row_last; ++row) a.table[(size_t)row * a.B + b] = rec;
+}
+
+int mg_lds_adapt(const LdsAdaptArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_lds_adapt, dim3((a.B + 255) / 256), dim3(256), 0, st, a);
+    MG_HIP(hipGetLastError());
+    return MGADMM_OK;
+}

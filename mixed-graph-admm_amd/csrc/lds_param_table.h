@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "mgadmm.h"
+#include "mg_hd.h"      // MG_HD: lhs_def_of and record_of also run on the device (k_lds_adapt, lds_adapt.h)
 
 // One record of the device table: the eight values a trip of k_admm_lds reads from LdsArgsCore, formed by the host from six
 // doubles with the expressions of the scalars (lds_fill_args)
@@ -25,7 +26,7 @@ struct LhsDef {
 };
 
 // the three left-hand sides of ADMM.py:366-399 from the weights, in double
-inline LhsDef lhs_def_of(int which, int ablation, double rho, double rho_u, double rho_d, double mu_u, double mu_d2) {
+MG_HD inline LhsDef lhs_def_of(int which, int ablation, double rho, double rho_u, double rho_d, double mu_u, double mu_d2) {
     switch (which) {
         case MGADMM_LHS_X:
             if (ablation == MGADMM_ABL_NONE) return {1, 1, (rho_u + rho_d) / 2, rho / 2};
@@ -62,7 +63,7 @@ inline double weight_of(const Source& s, int f, int row, int b) {
 }
 
 // the record of six doubles: lhs_def_of in double, then the casts
-inline LdsSampleParams record_of(int ablation, const double w[NW]) {
+MG_HD inline LdsSampleParams record_of(int ablation, const double w[NW]) {
     const LhsDef dx = lhs_def_of(MGADMM_LHS_X, ablation, w[0], w[1], w[2], w[3], w[5]);
     LdsSampleParams r;
     r.cx1 = (float)dx.c1; r.cx2 = (float)dx.c2;

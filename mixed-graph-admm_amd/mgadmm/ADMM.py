@@ -72,6 +72,57 @@ def _check_sample_params(sample_params, B):
     return out
 
 
+ADAPTIVE_RHO_KEYS = ("every", "mu", "tau", "until", "rho_min", "rho_max")
+
+
+def _check_adaptive_rho(adaptive_rho, adaptive_start=0):
+    """``adaptive_rho`` of ``solve``: dict with ``every`` (1 ... 16), ``mu`` > 1 (default 10), ``tau`` > 1 (default 2), ``until``
+    (None: no limit), ``rho_min`` / ``rho_max`` (a number for all three penalties, or three in the order rho, rho_u, rho_d, or a
+    dict by name; defaults 1e-6 / 1e6) -> the ``_lib.AdaptiveRho`` struct.  ValueError for what
+    ``mgadmm_solver_set_adaptive_rho`` refuses, found before the library is touched."""
+    if not hasattr(adaptive_rho, "items"):
+        raise ValueError(f"adaptive_rho must be a dict with keys out of {ADAPTIVE_RHO_KEYS}, got {type(adaptive_rho).__name__}")
+    for k2 in adaptive_rho:
+        if k2 not in ADAPTIVE_RHO_KEYS:
+            raise ValueError(f"adaptive_rho: unknown key {k2!r} (expected some of {ADAPTIVE_RHO_KEYS})")
+    if adaptive_rho.get("every") is None:
+        raise ValueError("adaptive_rho needs 'every' (iterations between two adaptation steps, 1 ... 16)")
+    every, start = int(adaptive_rho["every"]), int(adaptive_start)
+    until = adaptive_rho.get("until")
+    until = 0 if until is None else int(until)
+    mu, tau = float(adaptive_rho.get("mu", 10.0)), float(adaptive_rho.get("tau", 2.0))
+    if not 1 <= every <= 16:
+        raise ValueError(f"adaptive_rho: every = {every} outside [1, 16] (the iterations of one launch)")
+    if not mu > 1.0 or not tau > 1.0:
+        raise ValueError(f"adaptive_rho: mu = {mu} and tau = {tau} should both be > 1")
+    if until < 0:
+        raise ValueError(f"adaptive_rho: until = {until} is negative (None: no limit)")
+    if start < 0 or start % every:
+        raise ValueError(f"adaptive_start = {start} must be a non-negative multiple of every = {every}")
+
+    def three(name, default):
+        v = adaptive_rho.get(name)
+        if v is None:
+            return [default] * 3
+        if hasattr(v, "items"):
+            if set(v) - set(SAMPLE_PARAM_NAMES[:3]):
+                raise ValueError(f"adaptive_rho[{name!r}]: unknown keys {sorted(set(v) - set(SAMPLE_PARAM_NAMES[:3]))}")
+            return [float(v.get(nm, default)) for nm in SAMPLE_PARAM_NAMES[:3]]
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 0:
+            return [float(a)] * 3
+        if a.shape != (3,):
+            raise ValueError(f"adaptive_rho[{name!r}] must be a number, three numbers (rho, rho_u, rho_d) or a dict by name")
+        return [float(t) for t in a]
+    lo, hi = three("rho_min", 1e-6), three("rho_max", 1e6)
+    for nm, a, b in zip(SAMPLE_PARAM_NAMES[:3], lo, hi):
+        if not (0.0 < a <= b < float("inf")):
+            raise ValueError(f"adaptive_rho: rho_min[{nm}] = {a}, rho_max[{nm}] = {b}, should be 0 < rho_min <= rho_max (finite)")
+    ar = _lib.AdaptiveRho(every=every, until=until, mu=mu, tau=tau)
+    ar.rho_min[:], ar.rho_max[:] = lo, hi
+    return ar, start
+
+
 def _check_param_schedule(param_schedule, B, schedule_start=0, sample_params=None):
     """``param_schedule`` of ``solve``: dict name -> array of shape (K,) (shared form) or (K, B) (per-sample form), the same K
     and the same form for every name, as ``(dict name -> float64 array, K, 0 or B)``.  Raises ValueError for an unknown name,
@@ -172,6 +223,7 @@ class ADMM_algorithm():
                       iteration count of every sample in ``n_iters_per_sample``; the residual lists count a stopped
                       sample as standing still, ``delta_x_per_step`` stays empty.  LDS-resident float32 path only.
     """
+    rho_history = rho_final = None      # of the last solve(adaptive_rho=...)
 
     def __init__(self, graph_info, ADMM_info, use_kNN=False, k=4, u_sigma=None, d_sigma=None, expand_time_dim=True,
                  ablation='None', t_in=12, T=24, use_line_graph=False, skip_connection=1, *, device=None,
@@ -432,6 +484,19 @@ class ADMM_algorithm():
         finally:
             _lib.lib.mgadmm_solver_set_param_schedule(h, None, 0, 0, 0)
 
+    @contextlib.contextmanager
+    def _adaptive(self, h, ar):
+        """Adaptive penalties (``_check_adaptive_rho`` output) set on solver ``h`` for the solves inside the block and cleared
+        after it, like ``_sample_table``."""
+        if ar is None:
+            yield
+            return
+        _lib.check(_lib.lib.mgadmm_solver_set_adaptive_rho(h, C.byref(ar[0]), ar[1]))
+        try:
+            yield
+        finally:
+            _lib.lib.mgadmm_solver_set_adaptive_rho(h, None, 0)
+
     def _check_graph_sets(self, graph_sets, graph_of_sample, graph_params, B):
         """The graph arguments of ``solve`` as ``(sets, set_of_sample)`` -- a list of (u_ew, d_ew) tables and an int32 array of
         length B -- or None without them.  ValueError for what can be refused before the library is touched."""
@@ -656,7 +721,7 @@ class ADMM_algorithm():
 
     def solve(self, y, mask=None, differential=False, print_info=False, return_state=True, per_sample_history=False,
               warm_start=None, sample_params=None, graph_sets=None, graph_of_sample=None, graph_params=None,
-              param_schedule=None, schedule_start=0):
+              param_schedule=None, schedule_start=0, adaptive_rho=None, adaptive_start=0):
         """Run the ADMM loop and return ``(x, (zu, zd), phi, history)``; ``history`` is a dict with the
         same lists that are also stored on the instance (p_res_list, d_res_list, ...).
 
@@ -682,10 +747,24 @@ class ADMM_algorithm():
         scope of ``sample_params``).  Iteration k of this call solves with row ``min(schedule_start + k, K - 1)``; a name
         that is missing follows ``sample_params`` or the instance's scalar, a name given in both is refused.  K scheduled
         iterations equal K one-iteration solves chained with ``warm_start`` and the rows assigned as scalars, bit for bit;
-        ``schedule_start`` lets a resumed solve continue the schedule.  For this call only (``geometric_ramp`` builds a ramp)."""
+        ``schedule_start`` lets a resumed solve continue the schedule.  For this call only (``geometric_ramp`` builds a ramp).
+
+        ``adaptive_rho``: penalties adapted on the device by residual balancing -- a dict ``{'every': 4, 'mu': 10, 'tau': 2,
+        'until': None, 'rho_min': ..., 'rho_max': ...}`` (``_check_adaptive_rho``).  After every ``every``-th iteration each
+        sample raises a penalty by ``tau`` where its primal residual exceeds ``mu`` times the penalty-scaled dual residual, and
+        lowers it in the opposite case: (PRI_ZU, DUAL_ZU) -> rho_u, (PRI_PHI, DUAL_PHI) -> rho, (PRI_ZD, DUAL_ZD) -> rho_d.  The
+        start values are ``sample_params`` where given, otherwise the scalars.  Afterwards ``self.rho_history`` (P, 3, B) holds
+        rho, rho_u, rho_d by period (row 0 the start values; NaN past a sample's own stop) and ``self.rho_final`` (3, B) the last
+        values of every sample.  A resumed solve passes ``rho_final`` as ``sample_params`` and ``adaptive_start`` = the
+        iterations done (a multiple of ``every``).  LDS-resident float32 path only; not together with ``param_schedule``;
+        with ``check_stop`` it needs ``admm_convergence='per_sample'``.  For this call only."""
         sp = _check_sample_params(sample_params, y.shape[0]) if sample_params is not None else None
         sch = (_check_param_schedule(param_schedule, y.shape[0], schedule_start, sp) if param_schedule is not None else None)
         gs = self._check_graph_sets(graph_sets, graph_of_sample, graph_params, y.shape[0])
+        ar = _check_adaptive_rho(adaptive_rho, adaptive_start) if adaptive_rho is not None else None
+        if ar is not None and sch is not None:
+            raise ValueError("adaptive_rho and param_schedule exclude each other (the adaptation writes the table a schedule would fill)")
+        self.rho_history = self.rho_final = None
         if differential:
             assert mask is None, 'differential mode does not support mask'   # flag has no other effect (Q3)
         dt = self._dtype_for(y)
@@ -735,7 +814,8 @@ class ADMM_algorithm():
             be = np.full((I, 3, K, B), np.nan, dtype=np.float64)
             hs.cg_alpha = al.ctypes.data_as(C.POINTER(C.c_double))
             hs.cg_beta = be.ctypes.data_as(C.POINTER(C.c_double))
-        with self._sample_table(h, sp, B), self._graph_table(h, Cn, gs, B), self._schedule_table(h, sch, schedule_start):
+        with self._sample_table(h, sp, B), self._graph_table(h, Cn, gs, B), self._schedule_table(h, sch, schedule_start), \
+                self._adaptive(h, ar):
             if warm_start is None:
                 rc = _lib.lib.mgadmm_solve(h, _ptr(yd), _ptr(md), mask_f32, B, _ptr(x), C.byref(st), C.byref(hs),
                                            _stream_ptr(dev))
@@ -754,6 +834,8 @@ class ADMM_algorithm():
                                                 C.byref(st), C.byref(hs), _stream_ptr(dev))
         n = hs.n_iters
         self.n_iters_per_sample = nps
+        if ar is not None and rc in (_lib.OK, _lib.ERR_NONFINITE):
+            self._fetch_rho_history(h, B)
         if dxps is not None:
             dxps = dxps[:n]
         if rc == _lib.ERR_NONFINITE:
@@ -780,12 +862,29 @@ class ADMM_algorithm():
         self.state["x"] = xo
         return xo, (zu, zd), phi, self.history()
 
-    def combined_loop(self, y, mask=None, differential=False, print_info=True, sample_params=None, param_schedule=None, **graph_kw):
+    def _fetch_rho_history(self, h, B):
+        npd = C.c_int32(0)
+        _lib.check(_lib.lib.mgadmm_solver_get_adaptive_history(h, B, None, 0, C.byref(npd)))
+        hist = np.full((npd.value, 3, B), np.nan, dtype=np.float64)
+        if npd.value:
+            _lib.check(_lib.lib.mgadmm_solver_get_adaptive_history(h, B, hist.ctypes.data_as(C.POINTER(C.c_double)), npd.value, C.byref(npd)))
+        hist[np.isnan(hist)] = np.nan                         # (one NaN pattern)
+        while hist.shape[0] > 1 and np.isnan(hist[-1]).all():    # a step enqueued after the last sample had stopped
+            hist = hist[:-1]
+        self.rho_history = hist
+        if hist.shape[0]:
+            last = (~np.isnan(hist[:, 0, :])).sum(axis=0) - 1        # a sample's rows are NaN from its stop on
+            self.rho_final = np.ascontiguousarray(hist[last, :, np.arange(B)].T)
+
+    def combined_loop(self, y, mask=None, differential=False, print_info=True, sample_params=None, param_schedule=None,
+                      adaptive_rho=None, **graph_kw):
         """``y`` (B, t_in, N, C) [or (B, T, N, C) with ``mask``] -> ``x`` (B, T, N, C), dtype/device of y.
         History attributes are filled like the reference's (ADMM.py:612-643).  ``sample_params``, ``param_schedule`` and the
-        graph arguments (``graph_params``, ``graph_sets``, ``graph_of_sample``): see ``solve``."""
+        graph arguments (``graph_params``, ``graph_sets``, ``graph_of_sample``) and ``adaptive_rho``: see ``solve``."""
         if param_schedule is not None:
             graph_kw = dict(graph_kw, param_schedule=param_schedule)
+        if adaptive_rho is not None:
+            graph_kw = dict(graph_kw, adaptive_rho=adaptive_rho)
         return self.solve(y, mask=mask, differential=differential, print_info=print_info, return_state=False,
                           sample_params=sample_params, **graph_kw)[0]
 

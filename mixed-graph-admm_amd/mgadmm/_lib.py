@@ -84,6 +84,11 @@ class SampleParams(C.Structure):
 ParamSchedule = SampleParams       # mgadmm_param_schedule: the same six pointers, arrays of [n_rows][B] / [n_rows]
 
 
+class AdaptiveRho(C.Structure):    # mgadmm_adaptive_rho; rho_min / rho_max in the order rho, rho_u, rho_d
+    _fields_ = [("every", C.c_int32), ("until", C.c_int32), ("mu", C.c_double), ("tau", C.c_double),
+                ("rho_min", C.c_double * 3), ("rho_max", C.c_double * 3)]
+
+
 # every symbol include/mgadmm.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
 SYMBOLS = {
@@ -100,6 +105,8 @@ SYMBOLS = {
     "mgadmm_solver_set_sample_params": (C.c_int, [_vp, C.POINTER(SampleParams), C.c_int32]),
     "mgadmm_solver_set_sample_graphs": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp), _i32p, C.c_int32]),
     "mgadmm_solver_set_param_schedule": (C.c_int, [_vp, C.POINTER(SampleParams), C.c_int32, C.c_int32, C.c_int32]),
+    "mgadmm_solver_set_adaptive_rho": (C.c_int, [_vp, C.POINTER(AdaptiveRho), C.c_int32]),
+    "mgadmm_solver_get_adaptive_history": (C.c_int, [_vp, C.c_int32, _f64p, C.c_int32, _i32p]),
     "mgadmm_solver_workspace_bytes": (C.c_int64, [_vp]),
     "mgadmm_solver_path": (C.c_int, [_vp, C.c_int32]),
     "mgadmm_solver_query": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int64)]),
