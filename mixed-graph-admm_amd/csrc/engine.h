@@ -21,6 +21,7 @@
 #include "lds_graph_sets.h"
 #include "lds_param_table.h"
 #include "lds_schedule.h"
+#include "solve_gate.h"
 
 namespace {
 
@@ -93,17 +94,12 @@ struct Engine : EngineBase {
     int* d_pstop = nullptr;       // [Bp_max] stop words, [1] number of stopped samples, [Bp_max] iterations of every sample
     double* d_ps_full = nullptr;  // [max_admm_iter][NMETRIC][Bp]: per-sample metric sums of every iteration (allocated on first use)
     size_t ps_full_elems = 0;
-    // per-sample ADMM weights (mgadmm_solver_set_sample_params): the caller's arrays (empty = the scalar of `p`) and the device
-    // table of the records k_admm_lds_pp reads, rebuilt whenever the arrays or the scalars change
-    int sp_B = 0;                 // samples of the table; 0 = none set
-    std::vector<double> sp_val[6];   // rho, rho_u, rho_d, mu_u, mu_d1, mu_d2
+    // per-sample ADMM weights (mgadmm_solver_set_sample_params) and per-iteration weights (mgadmm_solver_set_param_schedule):
+    // the caller's arrays (solve_gate.h) and the device tables of the records k_admm_lds_pp reads.  d_sp: wt.sp_B records, rebuilt
+    // whenever the arrays or the scalars change; d_sch: wt.sch_rows x B records, formed when a solve starts and kept until
+    // something it was formed from changes
+    solvegate::WeightTables wt;
     LdsSampleParams* d_sp = nullptr;   // [Bmax]
-    // per-iteration weights (mgadmm_solver_set_param_schedule, lds_param_table.h): the caller's arrays ([sch_rows][sch_B], or
-    // [sch_rows] in the shared form sch_B = 0; empty = the weight follows the per-sample table or the scalar) and the device table
-    // of sch_rows x B records, formed when a solve starts and kept until something it was formed from changes
-    int sch_rows = 0;             // rows of the schedule; 0 = none set
-    int sch_B = 0, sch_row0 = 0;
-    std::vector<double> sch_val[6];
     LdsSampleParams* d_sch = nullptr;
     size_t sch_elems = 0;
     int sch_up_B = 0;             // batch the device table was formed for; 0 = it has to be formed
@@ -471,26 +467,16 @@ struct Engine : EngineBase {
         for (auto& e : ev_ring) MG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         MG_TRY(alloc_iter_dependent());
         MG_TRY(plan_lds());
-        return check_admm_convergence(p, "solver_create");
+        return refused(solvegate::admm_convergence_gate(facts(p), "solver_create"));
     }
 
-    // The per-sample stop test of the outer loop lives in the LDS-resident kernel (one workgroup owns a sample); the streaming
-    // kernels are batch-innermost and would need per-sample masks throughout (like MGADMM_CG_BATCH_MAX is streaming-only).
-    int check_admm_convergence(const mgadmm_params& np, const char* who) const {
-        MG_REQUIRE(np.admm_convergence == MGADMM_ADMM_WHOLE_BATCH || np.admm_convergence == MGADMM_ADMM_PER_SAMPLE,
-                   "%s: admm_convergence should be whole_batch (0) or per_sample (1), got %d", who, np.admm_convergence);
-        if (np.admm_convergence != MGADMM_ADMM_PER_SAMPLE) return MGADMM_OK;
-        const char* why = nullptr;
-        if (!std::is_same<S, float>::value) why = "float64 arithmetic runs on the streaming path";
-        else if (np.path == MGADMM_PATH_STREAM) why = "path is MGADMM_PATH_STREAM";
-        else if (np.cg_convergence == MGADMM_CG_BATCH_MAX) why = "cg_convergence batch_max runs on the streaming path";
-        else if (!lds.ok) why = "the LDS-resident path cannot hold this graph (it needs T*N*8 B + tables <= 160 KiB and N*G <= 1024)";
-        if (why) {
-            mg_set_error("%s: admm_convergence per_sample is implemented by the LDS-resident float32 path only: %s", who, why);
-            return MGADMM_ERR_UNSUPPORTED;
-        }
-        return MGADMM_OK;
+    // What this solver refuses is decided in solve_gate.h from these facts (with the parameters `q` in force or about to be
+    // set) and from what is set; the engine reports the answer
+    solvegate::Facts facts(const mgadmm_params& q) const {
+        return {std::is_same<S, float>::value, q.path, q.cg_convergence, q.admm_convergence, q.check_stop, lds.ok, g->mode == MGADMM_TEMPORAL_BAND, N, T};
     }
+    solvegate::SetState set_state() const { return {wt.sp_B, sg_B, wt.sch_rows, wt.sch_B, ad_on}; }
+    static int refused(const solvegate::Result& r) { if (r.rc != MGADMM_OK) mg_set_error("%s", r.msg.c_str()); return r.rc; }
 
     int alloc_iter_dependent() {
         auto fr = [](void* q) { if (q) (void)hipFree(q); };
@@ -524,11 +510,8 @@ struct Engine : EngineBase {
         MG_REQUIRE(np.cg_convergence == MGADMM_CG_PER_SAMPLE || np.cg_convergence == MGADMM_CG_BATCH_MAX,
                    "set_params: cg_convergence should be per_sample (0) or batch_max (1), got %d", np.cg_convergence);
         MG_REQUIRE(np.max_inner_iter >= 0, "set_params: max_inner_iter must be >= 0 (got %d)", np.max_inner_iter);
-        if (np.path == MGADMM_PATH_LDS && np.cg_convergence == MGADMM_CG_BATCH_MAX) {
-            mg_set_error("set_params: the LDS-resident path implements per-sample CG convergence only (batch_max: streaming path)");
-            return MGADMM_ERR_UNSUPPORTED;
-        }
-        MG_TRY(check_admm_convergence(np, "set_params"));
+        MG_TRY(refused(solvegate::set_params_gate(facts(np))));
+        MG_TRY(refused(solvegate::admm_convergence_gate(facts(np), "set_params")));
         if (np.rho != p.rho || np.rho_u != p.rho_u || np.rho_d != p.rho_d || np.mu_u != p.mu_u || np.mu_d1 != p.mu_d1 ||
             np.mu_d2 != p.mu_d2 || np.ablation != p.ablation)
             sch_up_B = 0;      // (the schedule's records follow the scalars where it names no weight)
@@ -536,154 +519,43 @@ struct Engine : EngineBase {
         sv->p = np;
         MG_HIP(hipSetDevice(g->device));
         MG_TRY(alloc_iter_dependent());
-        return sp_B > 0 ? upload_sample_params() : (int)MGADMM_OK;      // (fields that were not given follow the new scalars)
+        return wt.sp_B > 0 ? upload_sample_params() : (int)MGADMM_OK;      // (fields that were not given follow the new scalars)
     }
 
     // ---------------------------------------------------------------- per-sample ADMM weights
     int set_sample_params(const mgadmm_sample_params* sp, int B) override {
-        if (sp == nullptr || B == 0) {
-            sp_B = 0;
-            for (auto& v : sp_val) v.clear();
-            sch_up_B = 0;
-            return MGADMM_OK;
-        }
-        MG_REQUIRE(B >= 1 && B <= Bmax, "set_sample_params: batch %d outside [1, max_batch=%d]", B, Bmax);
-        static const char* const names[6] = {"rho", "rho_u", "rho_d", "mu_u", "mu_d1", "mu_d2"};
-        const double* const src[6] = {sp->rho, sp->rho_u, sp->rho_d, sp->mu_u, sp->mu_d1, sp->mu_d2};
-        if (sch_rows > 0) {
-            const bool in_sched[6] = {!sch_val[0].empty(), !sch_val[1].empty(), !sch_val[2].empty(), !sch_val[3].empty(),
-                                      !sch_val[4].empty(), !sch_val[5].empty()};
-            const char* twice = ldsparam::given_twice(in_sched, src);
-            MG_REQUIRE(!twice, "set_sample_params: %s is given twice, in the param_schedule that is set and in sample_params", twice);
-        }
-        for (int f = 0; f < 6; ++f) {
-            if (!src[f]) continue;
-            for (int b = 0; b < B; ++b) {
-                const double v = src[f][b];
-                MG_REQUIRE(std::isfinite(v), "set_sample_params: %s[%d] is not finite", names[f], b);
-                if (f < 3) MG_REQUIRE(v > 0.0, "set_sample_params: %s[%d] = %g, should be > 0", names[f], b, v);
-                else MG_REQUIRE(v >= 0.0, "set_sample_params: %s[%d] = %g, should be >= 0", names[f], b, v);
-            }
-        }
-        for (int f = 0; f < 6; ++f) {
-            if (src[f]) sp_val[f].assign(src[f], src[f] + B);
-            else sp_val[f].clear();
-        }
-        sp_B = B;
+        MG_TRY(refused(wt.set_sample(sp, B, Bmax)));      // (sp == nullptr or B == 0 clears)
         sch_up_B = 0;
+        if (wt.sp_B == 0) return MGADMM_OK;
         MG_HIP(hipSetDevice(g->device));
         return upload_sample_params();
     }
 
     // record b of the device table from sample b's six doubles: the expressions and casts solve_lds uses for the scalars
     // (n records; without a weights table -- a solve with a graph table alone -- every record holds the scalars)
-    int upload_sample_params() { return upload_sample_params(sp_B); }
+    int upload_sample_params() { return upload_sample_params(wt.sp_B); }
     int upload_sample_params(int n) {
         std::vector<LdsSampleParams> rec;
-        ldsparam::fill_records(weight_source(false), p.ablation, n, rec);      // (lds_param_table.h: one row, no schedule)
+        ldsparam::fill_records(wt.source(false, p), p.ablation, n, rec);      // (lds_param_table.h: one row, no schedule)
         if (!d_sp) MG_HIP(hipMalloc(&d_sp, sizeof(LdsSampleParams) * (size_t)Bmax));
         MG_HIP(hipMemcpy(d_sp, rec.data(), sizeof(LdsSampleParams) * rec.size(), hipMemcpyHostToDevice));
         return MGADMM_OK;
     }
 
-    // A solve with a table set: decided when the solve starts (table and parameters arrive in separate calls, in either
-    // order), before anything is enqueued.  The weights are read by the LDS-resident kernel only (one workgroup owns a sample).
-    int check_sample_params(int B) const {
-        MG_REQUIRE(B == sp_B, "solve: the sample_params table holds %d samples, the solve has B = %d", sp_B, B);
-        const char* why = nullptr;
-        if (!std::is_same<S, float>::value) why = "float64 arithmetic runs on the streaming path";
-        else if (p.path == MGADMM_PATH_STREAM) why = "path is MGADMM_PATH_STREAM";
-        else if (p.cg_convergence == MGADMM_CG_BATCH_MAX) why = "cg_convergence batch_max runs on the streaming path";
-        else if (!lds.ok) why = "the LDS-resident path cannot hold this graph (it needs T*N*8 B + tables <= 160 KiB and N*G <= 1024)";
-        if (why) {
-            mg_set_error("solve: sample_params (per-sample ADMM weights) are implemented by the LDS-resident float32 path only: %s", why);
-            return MGADMM_ERR_UNSUPPORTED;
-        }
-        if (p.check_stop && p.admm_convergence == MGADMM_ADMM_WHOLE_BATCH) {
-            mg_set_error("solve: sample_params with check_stop need admm_convergence per_sample (the whole_batch stop test would sum "
-                         "the residuals of different problems); or run a fixed count with check_stop = 0");
-            return MGADMM_ERR_UNSUPPORTED;
-        }
-        return MGADMM_OK;
-    }
-
     // ---------------------------------------------------------------- per-iteration weights
-    // where a (row, sample) takes its six weights from (lds_param_table.h): the schedule if `with_schedule`, the per-sample
-    // table, the scalars
-    ldsparam::Source weight_source(bool with_schedule) const {
-        ldsparam::Source src;
-        const double scalar[6] = {p.rho, p.rho_u, p.rho_d, p.mu_u, p.mu_d1, p.mu_d2};
-        for (int f = 0; f < 6; ++f) {
-            src.scalar[f] = scalar[f];
-            src.sample[f] = sp_B > 0 && !sp_val[f].empty() ? sp_val[f].data() : nullptr;
-            src.sched[f] = with_schedule && sch_rows > 0 && !sch_val[f].empty() ? sch_val[f].data() : nullptr;
-        }
-        if (with_schedule && sch_rows > 0) { src.n_rows = sch_rows; src.sched_B = sch_B; }
-        return src;
-    }
-
     // Iteration k of the following solves reads row min(first_row + k, n_rows - 1) of the six arrays ([n_rows][B] row-major, or
     // [n_rows] with B == 0: every sample reads the same row); a null array follows the per-sample table or the scalar.
     // Synchronous like set_sample_graphs: the old device table is freed after the device has finished whatever read it.
     int set_param_schedule(const mgadmm_param_schedule* sch, int n_rows, int B, int first_row) override {
         MG_HIP(hipSetDevice(g->device));
-        if (sch == nullptr || n_rows == 0) {
-            if (d_sch) {
-                MG_HIP(hipDeviceSynchronize());
-                (void)hipFree(d_sch);
-                d_sch = nullptr;
-                sch_elems = 0;
-            }
-            sch_rows = sch_B = sch_row0 = sch_up_B = 0;
-            for (auto& v : sch_val) v.clear();
-            return MGADMM_OK;
+        if ((sch == nullptr || n_rows == 0) && d_sch) {      // clears
+            MG_HIP(hipDeviceSynchronize());
+            (void)hipFree(d_sch);
+            d_sch = nullptr;
+            sch_elems = 0;
         }
-        MG_REQUIRE(n_rows >= 1 && n_rows <= (1 << 20), "set_param_schedule: n_rows %d outside [1, 2^20]", n_rows);
-        MG_REQUIRE(B >= 0 && B <= Bmax, "set_param_schedule: batch %d outside [0 (shared form), max_batch=%d]", B, Bmax);
-        MG_REQUIRE(first_row >= 0, "set_param_schedule: first_row %d is negative", first_row);
-        MG_REQUIRE((int64_t)n_rows * Bmax <= (int64_t)1 << 27, "set_param_schedule: n_rows %d x max_batch %d records exceed 2^27", n_rows, Bmax);
-        const double* const src[6] = {sch->rho, sch->rho_u, sch->rho_d, sch->mu_u, sch->mu_d1, sch->mu_d2};
-        std::string why;
-        if (!ldsparam::validate("set_param_schedule: param_schedule", src, n_rows, B, why)) {
-            mg_set_error("%s", why.c_str());
-            return MGADMM_ERR_INVALID;
-        }
-        if (sp_B > 0) {
-            const bool in_table[6] = {!sp_val[0].empty(), !sp_val[1].empty(), !sp_val[2].empty(), !sp_val[3].empty(), !sp_val[4].empty(),
-                                      !sp_val[5].empty()};
-            const char* twice = ldsparam::given_twice(src, in_table);
-            MG_REQUIRE(!twice, "set_param_schedule: %s is given twice, in param_schedule and in the sample_params table that is set", twice);
-        }
-        const size_t n = (size_t)n_rows * (B > 0 ? B : 1);
-        for (int f = 0; f < 6; ++f) {
-            if (src[f]) sch_val[f].assign(src[f], src[f] + n);
-            else sch_val[f].clear();
-        }
-        sch_rows = n_rows; sch_B = B; sch_row0 = first_row; sch_up_B = 0;
-        return MGADMM_OK;
-    }
-
-    // A solve with a schedule set: decided when the solve starts, before anything is enqueued.  The per-sample form is read by
-    // the LDS-resident kernel only (the refusals of check_sample_params); the shared form runs on both paths and with the
-    // whole-batch stop test (every sample solves the same problem)
-    int check_param_schedule(int B) const {
-        if (sch_B == 0) return MGADMM_OK;
-        MG_REQUIRE(B == sch_B, "solve: the param_schedule table holds %d samples per row, the solve has B = %d", sch_B, B);
-        const char* why = nullptr;
-        if (!std::is_same<S, float>::value) why = "float64 arithmetic runs on the streaming path";
-        else if (p.path == MGADMM_PATH_STREAM) why = "path is MGADMM_PATH_STREAM";
-        else if (p.cg_convergence == MGADMM_CG_BATCH_MAX) why = "cg_convergence batch_max runs on the streaming path";
-        else if (!lds.ok) why = "the LDS-resident path cannot hold this graph (it needs T*N*8 B + tables <= 160 KiB and N*G <= 1024)";
-        if (why) {
-            mg_set_error("solve: the per-sample form of param_schedule (one column per sample) is implemented by the LDS-resident float32 "
-                         "path only: %s; the shared form (B = 0) runs on both paths", why);
-            return MGADMM_ERR_UNSUPPORTED;
-        }
-        if (p.check_stop && p.admm_convergence == MGADMM_ADMM_WHOLE_BATCH) {
-            mg_set_error("solve: the per-sample form of param_schedule with check_stop needs admm_convergence per_sample (the whole_batch "
-                         "stop test would sum the residuals of different problems); or run a fixed count with check_stop = 0");
-            return MGADMM_ERR_UNSUPPORTED;
-        }
+        MG_TRY(refused(wt.set_schedule(sch, n_rows, B, first_row, Bmax)));
+        sch_up_B = 0;
         return MGADMM_OK;
     }
 
@@ -691,7 +563,7 @@ struct Engine : EngineBase {
     int upload_param_schedule(int B) {
         if (sch_up_B == B && d_sch) return MGADMM_OK;
         std::vector<LdsSampleParams> rec;
-        ldsparam::fill_records(weight_source(true), p.ablation, B, rec);
+        ldsparam::fill_records(wt.source(true, p), p.ablation, B, rec);
         MG_TRY(grow(d_sch, sch_elems, rec.size()));
         MG_HIP(hipMemcpy(d_sch, rec.data(), sizeof(LdsSampleParams) * rec.size(), hipMemcpyHostToDevice));
         sch_up_B = B;
@@ -716,32 +588,6 @@ struct Engine : EngineBase {
             return MGADMM_ERR_INVALID;
         }
         ad = q; ad_start = start; ad_on = true;
-        return MGADMM_OK;
-    }
-
-    // A solve with adaptive penalties set: decided when the solve starts, before anything is enqueued.  The step runs between
-    // launches of the LDS-resident kernel and writes the table only k_admm_lds_pp reads
-    int check_adaptive(int B) const {
-        const char* why = nullptr;
-        if (!std::is_same<S, float>::value) why = "float64 arithmetic runs on the streaming path";
-        else if (p.path == MGADMM_PATH_STREAM) why = "path is MGADMM_PATH_STREAM";
-        else if (p.cg_convergence == MGADMM_CG_BATCH_MAX) why = "cg_convergence batch_max runs on the streaming path";
-        else if (!lds.ok) why = "the LDS-resident path cannot hold this graph (it needs T*N*8 B + tables <= 160 KiB and N*G <= 1024)";
-        if (why) {
-            mg_set_error("solve: adaptive_rho (penalties adapted on the device) is implemented by the LDS-resident float32 path only: %s", why);
-            return MGADMM_ERR_UNSUPPORTED;
-        }
-        if (p.check_stop && p.admm_convergence == MGADMM_ADMM_WHOLE_BATCH) {
-            mg_set_error("solve: adaptive_rho with check_stop needs admm_convergence per_sample (every sample carries its own penalties: "
-                         "the whole_batch stop test would sum the residuals of different problems); or run a fixed count with check_stop = 0");
-            return MGADMM_ERR_UNSUPPORTED;
-        }
-        if (sch_rows > 0) {
-            mg_set_error("solve: adaptive_rho and a param_schedule are both set: the adaptation writes the table a schedule would fill");
-            return MGADMM_ERR_UNSUPPORTED;
-        }
-        MG_REQUIRE(sp_B == 0 || B == sp_B, "solve: adaptive_rho takes its start values from the sample_params table of %d samples, the solve has B = %d",
-                   sp_B, B);
         return MGADMM_OK;
     }
 
@@ -786,14 +632,7 @@ struct Engine : EngineBase {
             MG_REQUIRE(q->reorder == g->reorder && q->has_perm == g->has_perm && q->perm == g->perm,
                        "set_sample_graphs: graphs[%d] has another internal node order than the solver's graph", s);
         }
-        const char* why = nullptr;
-        if (!std::is_same<S, float>::value) why = "float64 arithmetic runs on the streaming path";
-        else if (!lds.ok) why = "the LDS-resident path cannot hold this graph (it needs T*N*8 B + tables <= 160 KiB and N*G <= 1024)";
-        else if (g->mode == MGADMM_TEMPORAL_BAND) why = "a band graph (line graph) has no W_d tables to vary";
-        if (why) {
-            mg_set_error("set_sample_graphs: sample_graphs (per-sample graph weights) are implemented by the LDS-resident float32 path only: %s", why);
-            return MGADMM_ERR_UNSUPPORTED;
-        }
+        MG_TRY(refused(solvegate::set_sample_graphs_gate(facts(p))));
         // plan every set (the bank search of a set takes as long as the solver's own: sets are planned side by side)
         std::vector<ldsplan::Input> sets;
         for (int s = 0; s < n_sets; ++s)
@@ -821,27 +660,6 @@ struct Engine : EngineBase {
         if (d_sg_img) (void)hipFree(d_sg_img);
         d_sg_img = fresh;
         sg_B = B; sg_sets = n_sets;
-        return MGADMM_OK;
-    }
-
-    // A solve with a graph table set: the refusals of check_sample_params, before anything is enqueued
-    int check_sample_graphs(int B) const {
-        MG_REQUIRE(B == sg_B, "solve: the sample_graphs table holds %d samples, the solve has B = %d", sg_B, B);
-        const char* why = nullptr;
-        if (!std::is_same<S, float>::value) why = "float64 arithmetic runs on the streaming path";
-        else if (p.path == MGADMM_PATH_STREAM) why = "path is MGADMM_PATH_STREAM";
-        else if (p.cg_convergence == MGADMM_CG_BATCH_MAX) why = "cg_convergence batch_max runs on the streaming path";
-        else if (!lds.ok) why = "the LDS-resident path cannot hold this graph (it needs T*N*8 B + tables <= 160 KiB and N*G <= 1024)";
-        else if (g->mode == MGADMM_TEMPORAL_BAND) why = "a band graph (line graph) has no W_d tables to vary";
-        if (why) {
-            mg_set_error("solve: sample_graphs (per-sample graph weights) are implemented by the LDS-resident float32 path only: %s", why);
-            return MGADMM_ERR_UNSUPPORTED;
-        }
-        if (p.check_stop && p.admm_convergence == MGADMM_ADMM_WHOLE_BATCH) {
-            mg_set_error("solve: sample_graphs with check_stop need admm_convergence per_sample (the whole_batch stop test would sum "
-                         "the residuals of different problems); or run a fixed count with check_stop = 0");
-            return MGADMM_ERR_UNSUPPORTED;
-        }
         return MGADMM_OK;
     }
 
@@ -1464,16 +1282,9 @@ struct Engine : EngineBase {
         if (state_in) MG_TRY(check_state_in(x0, state_in));
         st = s;
         ad_last_periods = 0;
-        if (ad_on) MG_TRY(check_adaptive(B));
-        if (sp_B > 0) MG_TRY(check_sample_params(B));
-        if (sg_B > 0) MG_TRY(check_sample_graphs(B));
-        if (sch_rows > 0) MG_TRY(check_param_schedule(B));
-        if (p.path == MGADMM_PATH_LDS && !lds.ok) {
-            mg_set_error("solve: the LDS-resident path needs float32, T*N*8 B + CSR <= 160 KiB and N*G <= 1024 (N=%d, T=%d)", N, T);
-            return MGADMM_ERR_UNSUPPORTED;
-        }
+        MG_TRY(refused(solvegate::solve_gate(facts(p), set_state(), B)));      // (before anything is enqueued; its order of refusals: solve_gate.h)
         if (use_lds()) return solve_lds(y, mask, B, x0, state_in, x_out, state_out, hist);
-        MG_TRY(check_admm_convergence(p, "solve"));       // (refused at solver_create / set_params already)
+        MG_TRY(refused(solvegate::admm_convergence_gate(facts(p), "solve")));       // (refused at solver_create / set_params already)
         const Geom q = make_geom(B);
         MG_TRY(ensure_partials(q));
         const size_t ne = velems(q);
@@ -1522,13 +1333,13 @@ struct Engine : EngineBase {
             MG_HIP(hipMemcpyAsync(vec[zdc], vec[xc], ne * sizeof(S), hipMemcpyDeviceToDevice, st));
         }
 
-        // the six weights of an iteration: the row of the schedule (shared form: check_param_schedule) or the scalars of `p`
-        const ldsparam::Source wsrc = weight_source(true);
+        // the six weights of an iteration: the row of the schedule (the shared form: solve_gate let no other through) or the scalars of `p`
+        const ldsparam::Source wsrc = wt.source(true, p);
         int n_done = 0;
         int rc_final = MGADMM_OK;
         for (int it = 0; it < max_it; ++it) {
             double w[6];
-            ldsparam::row_weights(wsrc, it, sch_row0, w);
+            ldsparam::row_weights(wsrc, it, wt.sch_row0, w);
             const S rho = (S)w[0], rho_u = (S)w[1], rho_d = (S)w[2];
             auto lhs_of = [&](int which) { return lhs_def_of(which, p.ablation, w[0], w[1], w[2], w[3], w[5]); };
             // ---- RHS_x (ADMM.py:556-564)
@@ -1918,7 +1729,7 @@ struct Engine : EngineBase {
     // table where one is set, otherwise the scalars), period 0 of the history the start penalties, the later periods NaN
     int adapt_begin(LdsRun& r) {
         const int B = r.B, max_it = r.s.max_it;
-        const ldsparam::Source src = weight_source(false);
+        const ldsparam::Source src = wt.source(false, p);
         std::vector<LdsSampleParams> row, rec;
         ldsparam::fill_records(src, p.ablation, B, row);      // (one row: no schedule)
         rec.reserve((size_t)max_it * B);
@@ -1934,8 +1745,6 @@ struct Engine : EngineBase {
         MG_HIP(hipMemcpy(d_ad_w, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice));
         MG_HIP(hipMemcpy(d_ad_hist, w.data(), sizeof(double) * 3 * B, hipMemcpyHostToDevice));
         MG_HIP(hipMemsetAsync(d_ad_hist + (size_t)3 * B, 0xFF, sizeof(double) * (hist_rows - 1) * 3 * B, st));      // (all bits set: a NaN)
-        r.a.sp = d_ad_tab;
-        r.a.sp_rows = max_it; r.a.sp_row0 = 0; r.a.sp_stride = B;
         ad_last_B = B;
         return MGADMM_OK;
     }
@@ -2104,18 +1913,20 @@ struct Engine : EngineBase {
             if (s.per_sample) {
                 r.a.pstop = d_pstop; r.a.pstop_count = d_pstop + Bp_max; r.a.x_final = r.xo; r.a.admm_tol = p.admm_tol;
             }
-            if (sp_B > 0) r.a.sp = d_sp;      // (B == sp_B: check_sample_params) the launches take the kernels k_admm_lds_pp
-            if (sg_B > 0) {                   // (B == sg_B: check_sample_graphs) workgroup b reads the image of set d_sg_set[b]
-                if (sp_B == 0) MG_TRY(upload_sample_params(B));      // no weights table: records of the scalars, the same kernels
-                r.a.sp = d_sp;
+            if (sg_B > 0) {                   // (B == sg_B: solve_gate) workgroup b reads the image of set d_sg_set[b]
                 r.a.csr = d_sg_img; r.a.img_stride = ldssets::img_stride(lds); r.a.gset = d_sg_set;
             }
-            if (sch_rows > 0) {               // (check_param_schedule) trip k of a launch reads row sched_row(it0 + k, ...) of sch_rows x B records
-                MG_TRY(upload_param_schedule(B));
-                r.a.sp = d_sch;
-                r.a.sp_rows = sch_rows; r.a.sp_row0 = sch_row0; r.a.sp_stride = B;
+            // the table of records the launches read (with one they take the kernels k_admm_lds_pp); trip k of a launch reads
+            // row sched_row(it0 + k, sp_row0, sp_rows) of it
+            const solvegate::TableChoice tc = solvegate::table_of(set_state(), wt.sch_row0, s.max_it);
+            if (tc.scalar_records) MG_TRY(upload_sample_params(B));      // (a graph table without a weights table)
+            switch (tc.table) {
+                case solvegate::TABLE_NONE: break;
+                case solvegate::TABLE_SAMPLE: r.a.sp = d_sp; break;      // (B == sp_B: solve_gate)
+                case solvegate::TABLE_SCHEDULE: MG_TRY(upload_param_schedule(B)); r.a.sp = d_sch; break;
+                case solvegate::TABLE_ADAPTIVE: MG_TRY(adapt_begin(r)); r.a.sp = d_ad_tab; break;      // the steps between the launches write it
             }
-            if (ad_on) MG_TRY(adapt_begin(r));      // (check_adaptive) the table the steps between the launches write
+            r.a.sp_rows = tc.sp_rows; r.a.sp_row0 = tc.sp_row0; r.a.sp_stride = tc.stride_B ? B : 0;
             MG_TRY(chunked ? lds_run_chunks(r) : lds_run_steps(r));
             std::vector<int> nps;         // per-sample stop: iterations of every sample
             if (s.per_sample) MG_TRY(lds_finish_per_sample(r, nps));
