@@ -1,6 +1,8 @@
 // Solver engine: host-side orchestration of the ADMM loop of reference ADMM.py:511-648 over the streaming HIP kernels
-// (stream_kernels.h) and the LDS-resident fused kernel (lds_launch.hip).  Included by solver_f32.hip and solver_f64.hip,
-// which instantiate it for one scalar type each (separate translation units: the library builds in parallel).
+// (stream_kernels.h) for either scalar type, with what a solver of either type answers about the LDS-resident float32 path
+// (the plan record, the host state of the per-sample features, the refusals of solve_gate.h).  That path's driver is LdsEngine
+// (lds_engine.h), derived from Engine<float>: solver_f32.hip creates it, solver_f64.hip the plain Engine<double> (separate
+// translation units: the library builds in parallel).
 #pragma once
 #include <math.h>
 #include <cmath>
@@ -8,7 +10,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <thread>
 #include <type_traits>
 
 #include "common.h"
@@ -16,11 +17,9 @@
 #include "tile_meta.h"
 #include "stream_keys.h"
 #include "stream_kernels.h"
-#include "lds_args.h"
+#include "lds_adapt.h"      // ldsadapt::Params, validate: set_adaptive_rho checks its arguments for either scalar type
 #include "lds_plan.h"
-#include "lds_graph_sets.h"
 #include "lds_param_table.h"
-#include "lds_schedule.h"
 #include "solve_gate.h"
 
 namespace {
@@ -45,7 +44,6 @@ struct Engine : EngineBase {
 
     S* vec[V_COUNT] = {nullptr};
     S* vec_pool = nullptr;
-    int dev_cus = 0;               // compute units of the device (staggered start of k_admm_lds)
     size_t vec_elems = 0;
     S* partials = nullptr;
     size_t partials_elems = 0;
@@ -80,59 +78,20 @@ struct Engine : EngineBase {
     int cur_P = 0;                // partial rows written by the last row-kernel launch (k_rows or k_tile)
     int use_tile = 1;             // LDS-tiled spatial kernel on cluster-ordered graphs (reorder = 2); MGADMM_TILE=0 disables
     int64_t ws_bytes = 0;
-    // LDS-resident fused path (float32, small graphs)
-    using LdsPlan = ldsplan::LdsPlan;
-    LdsPlan lds;
-    int* d_lds_csr = nullptr;
-    double* d_m2 = nullptr;
-    // ADMM outer loop of the LDS path without host round trips (solve_lds): device stop word, second metric buffer, helper
-    // stream for the whole-batch metric kernels and the events that order the two streams
-    int lds_async = 1;            // MGADMM_LDS_ASYNC=0: one stream, the host tests the stop criterion after every iteration
-    int* d_stop = nullptr;
-    double* d_ps_ring = nullptr;  // [LDS_SETS][J][NMETRIC][Bp]: per-sample metric sums of the chunked schedule
-    // per-sample stop of the outer loop (MGADMM_ADMM_PER_SAMPLE)
-    int* d_pstop = nullptr;       // [Bp_max] stop words, [1] number of stopped samples, [Bp_max] iterations of every sample
-    double* d_ps_full = nullptr;  // [max_admm_iter][NMETRIC][Bp]: per-sample metric sums of every iteration (allocated on first use)
-    size_t ps_full_elems = 0;
-    // per-sample ADMM weights (mgadmm_solver_set_sample_params) and per-iteration weights (mgadmm_solver_set_param_schedule):
-    // the caller's arrays (solve_gate.h) and the device tables of the records k_admm_lds_pp reads.  d_sp: wt.sp_B records, rebuilt
-    // whenever the arrays or the scalars change; d_sch: wt.sch_rows x B records, formed when a solve starts and kept until
-    // something it was formed from changes
-    solvegate::WeightTables wt;
-    LdsSampleParams* d_sp = nullptr;   // [Bmax]
-    LdsSampleParams* d_sch = nullptr;
-    size_t sch_elems = 0;
-    int sch_up_B = 0;             // batch the device table was formed for; 0 = it has to be formed
-    // adaptive penalties (mgadmm_solver_set_adaptive_rho, lds_adapt.h): the parameters, and per solve the table of
-    // max_admm_iter x B records k_lds_adapt writes between the launches, the six weights of every sample as doubles and the
-    // history of the three penalties by period
-    bool ad_on = false;
-    ldsadapt::Params ad;
-    int ad_start = 0;
-    LdsSampleParams* d_ad_tab = nullptr;
-    double *d_ad_w = nullptr, *d_ad_hist = nullptr;
-    size_t ad_tab_elems = 0, ad_w_elems = 0, ad_hist_elems = 0;
-    int ad_last_B = 0, ad_last_periods = 0;   // of the last solve (mgadmm_solver_get_adaptive_history); 0 periods: it did not adapt
-    // per-sample graph weights (mgadmm_solver_set_sample_graphs, lds_graph_sets.h): the images of the sets back to back and the
-    // set of every sample; the solver's own image and the planner's switches are kept for the comparison with every set
-    int sg_B = 0, sg_sets = 0;    // samples / sets of the table; sg_B = 0: none set
-    int* d_sg_img = nullptr;      // [sg_sets][img_stride]
-    int* d_sg_set = nullptr;      // [Bp_max]
-    std::vector<int> lds_img_host;
-    ldsplan::Switches lds_sw;
-    // iterate buffers of solve_lds by slot number (lds_schedule.h): the 15 workspace vectors this path does not use otherwise
-    // hold the LDS_SETS (J - 1) + LDS_NBOUND = 13 slots of J = 4; chunks longer than 4 iterations (up to LDS_MAXJ) get the
-    // rest in lds_ring_extra on the first solve that asks for them, kept for the solver's lifetime
-    static constexpr int ring_ids[] = {V_XA, V_XB, V_ZUB, V_ZDB, V_PHIB, V_Y, V_MASK, V_R, V_P, V_Q, V_AP, V_RHS, V_TMP, V_IO0, V_IO1};
-    static constexpr int NRING = (int)(sizeof(ring_ids) / sizeof(ring_ids[0]));
-    std::vector<float*> lds_ring_extra;
+    // LDS-resident fused path (float32, small graphs): the plan record (none for float64), what the queries report of its last
+    // launch, and the host state of the per-sample features solve_gate.h decides on.  The device side: LdsEngine (lds_engine.h)
+    ldsplan::LdsPlan lds;
+    int lds_chunk = LDS_MAXJ;   // MGADMM_LDS_CHUNK: ADMM iterations per k_admm_lds launch when the iteration count is fixed (1 .. LDS_MAXJ)
     int64_t lds_instance = -1;       // MGADMM_Q_LDS_INSTANCE: template arguments of the k_admm_lds instance of the last launch
     int lds_unit = -1;               // MGADMM_Q_LDS_UNIT: which compilation of the instances it came from (0 / 1 / 2 = k_admm_lds / _ps / _pp)
+    solvegate::WeightTables wt;      // the caller's arrays of set_sample_params and set_param_schedule
+    bool ad_on = false;              // adaptive penalties (mgadmm_solver_set_adaptive_rho, lds_adapt.h): the parameters
+    ldsadapt::Params ad;
+    int ad_start = 0;
+    int ad_last_periods = 0;         // of the last solve (mgadmm_solver_get_adaptive_history); 0 periods: it did not adapt
+    int sg_B = 0;                    // samples of the graph table (mgadmm_solver_set_sample_graphs); 0: none set
     StreamKeyLog stream_keys;        // MGADMM_Q_STREAM_KEYS / _KEY0 + i: distinct k_rows / k_tile / k_cldr instances launched (stream_keys.h)
     static constexpr bool IS_F64 = std::is_same<S, double>::value;
-    int lds_chunk = LDS_MAXJ;   // MGADMM_LDS_CHUNK: ADMM iterations per k_admm_lds launch when the iteration count is fixed (1 .. LDS_MAXJ)
-    hipStream_t st_side = nullptr;
-    hipEvent_t ev_main[LDS_NBOUND] = {nullptr}, ev_side[LDS_NBOUND] = {nullptr};
     // profiling
     bool prof_on = false;
     std::vector<hipEvent_t> prof_ev;
@@ -154,12 +113,7 @@ struct Engine : EngineBase {
         auto fr = [](void* q) { if (q) (void)hipFree(q); };
         fr(vec_pool); fr(partials); fr(d_rr); fr(d_alpha); fr(d_beta); fr(d_alpha_hist); fr(d_beta_hist);
         fr(d_active); fr(d_iters_tmp); fr(d_nact); fr(d_nonfinite); fr(d_ps); fr(d_hist); fr(d_dxps);
-        fr(d_dxpart); fr(d_hist_ps); fr(d_cg_iters); fr(d_lds_csr); fr(d_m2); fr(d_stop); fr(d_ps_ring); fr(d_pstop); fr(d_ps_full);
-        fr(d_sp); fr(d_sg_img); fr(d_sg_set); fr(d_sch); fr(d_ad_tab); fr(d_ad_w); fr(d_ad_hist);
-        for (float* b : lds_ring_extra) if (b) (void)hipFree(b);
-        if (st_side) (void)hipStreamDestroy(st_side);
-        for (auto& e : ev_main) if (e) (void)hipEventDestroy(e);
-        for (auto& e : ev_side) if (e) (void)hipEventDestroy(e);
+        fr(d_dxpart); fr(d_hist_ps); fr(d_cg_iters);
         for (auto& tmd : tmeta) { fr(tmd.tl_col); fr(tmd.tl_w); fr(tmd.halo); fr(tmd.h_rowptr); fr(tmd.h_col); fr(tmd.h_val); }
         fr(cldr_dev.n0); fr(cldr_dev.nC); fr(cldr_dev.rows); fr(cldr_dev.dcol); fr(cldr_dev.dcnt); fr(cldr_dev.tcol); fr(cldr_dev.tcnt);
         fr(cldr_dev.dw); fr(cldr_dev.tw);
@@ -433,7 +387,8 @@ struct Engine : EngineBase {
         return MGADMM_OK;
     }
 
-    int init() override {
+    // the workspace and the buffers of the streaming path, which the LDS path borrows (LdsEngine::init plans after it)
+    int init_workspace() {
         MG_HIP(hipSetDevice(g->device));
         if (const char* e = getenv("MGADMM_WANT_BLOCKS")) want_blocks = std::max(64, atoi(e));
         if (const char* e = getenv("MGADMM_TILE")) use_tile = atoi(e);
@@ -442,7 +397,6 @@ struct Engine : EngineBase {
         if (const char* e = getenv("MGADMM_FOLD_LU")) use_fold_lu = atoi(e);
         if (const char* e = getenv("MGADMM_SWEEP_REV")) sweep_rev = atoi(e);
         if (const char* e = getenv("MGADMM_CLDR_ORDER")) cldr_tile_major = atoi(e);
-        if (const char* e = getenv("MGADMM_LDS_ASYNC")) lds_async = atoi(e);
         if (const char* e = getenv("MGADMM_LDS_CHUNK")) lds_chunk = std::max(1, std::min(atoi(e), LDS_MAXJ));
         Geom q = make_geom(Bmax);
         Bp_max = q.Bp;
@@ -465,8 +419,10 @@ struct Engine : EngineBase {
         MG_HIP(hipHostMalloc(&h_row, sizeof(double) * (MGADMM_NMETRIC + 1)));
         MG_HIP(hipHostMalloc(&h_flag, sizeof(int) * 4));
         for (auto& e : ev_ring) MG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        MG_TRY(alloc_iter_dependent());
-        MG_TRY(plan_lds());
+        return alloc_iter_dependent();
+    }
+    int init() override {
+        MG_TRY(init_workspace());
         return refused(solvegate::admm_convergence_gate(facts(p), "solver_create"));
     }
 
@@ -512,72 +468,29 @@ struct Engine : EngineBase {
         MG_REQUIRE(np.max_inner_iter >= 0, "set_params: max_inner_iter must be >= 0 (got %d)", np.max_inner_iter);
         MG_TRY(refused(solvegate::set_params_gate(facts(np))));
         MG_TRY(refused(solvegate::admm_convergence_gate(facts(np), "set_params")));
-        if (np.rho != p.rho || np.rho_u != p.rho_u || np.rho_d != p.rho_d || np.mu_u != p.mu_u || np.mu_d1 != p.mu_d1 ||
-            np.mu_d2 != p.mu_d2 || np.ablation != p.ablation)
-            sch_up_B = 0;      // (the schedule's records follow the scalars where it names no weight)
         p = np;
         sv->p = np;
         MG_HIP(hipSetDevice(g->device));
-        MG_TRY(alloc_iter_dependent());
-        return wt.sp_B > 0 ? upload_sample_params() : (int)MGADMM_OK;      // (fields that were not given follow the new scalars)
+        return alloc_iter_dependent();
     }
 
-    // ---------------------------------------------------------------- per-sample ADMM weights
+    // ---------------------------------------------------------------- per-sample and per-iteration ADMM weights
+    // The host half: the caller's arrays are checked and kept (solve_gate.h); LdsEngine forms the device tables from them
     int set_sample_params(const mgadmm_sample_params* sp, int B) override {
-        MG_TRY(refused(wt.set_sample(sp, B, Bmax)));      // (sp == nullptr or B == 0 clears)
-        sch_up_B = 0;
-        if (wt.sp_B == 0) return MGADMM_OK;
-        MG_HIP(hipSetDevice(g->device));
-        return upload_sample_params();
+        return refused(wt.set_sample(sp, B, Bmax));      // (sp == nullptr or B == 0 clears)
     }
-
-    // record b of the device table from sample b's six doubles: the expressions and casts solve_lds uses for the scalars
-    // (n records; without a weights table -- a solve with a graph table alone -- every record holds the scalars)
-    int upload_sample_params() { return upload_sample_params(wt.sp_B); }
-    int upload_sample_params(int n) {
-        std::vector<LdsSampleParams> rec;
-        ldsparam::fill_records(wt.source(false, p), p.ablation, n, rec);      // (lds_param_table.h: one row, no schedule)
-        if (!d_sp) MG_HIP(hipMalloc(&d_sp, sizeof(LdsSampleParams) * (size_t)Bmax));
-        MG_HIP(hipMemcpy(d_sp, rec.data(), sizeof(LdsSampleParams) * rec.size(), hipMemcpyHostToDevice));
-        return MGADMM_OK;
-    }
-
-    // ---------------------------------------------------------------- per-iteration weights
     // Iteration k of the following solves reads row min(first_row + k, n_rows - 1) of the six arrays ([n_rows][B] row-major, or
-    // [n_rows] with B == 0: every sample reads the same row); a null array follows the per-sample table or the scalar.
-    // Synchronous like set_sample_graphs: the old device table is freed after the device has finished whatever read it.
+    // [n_rows] with B == 0: every sample reads the same row); a null array follows the per-sample table or the scalar
     int set_param_schedule(const mgadmm_param_schedule* sch, int n_rows, int B, int first_row) override {
         MG_HIP(hipSetDevice(g->device));
-        if ((sch == nullptr || n_rows == 0) && d_sch) {      // clears
-            MG_HIP(hipDeviceSynchronize());
-            (void)hipFree(d_sch);
-            d_sch = nullptr;
-            sch_elems = 0;
-        }
-        MG_TRY(refused(wt.set_schedule(sch, n_rows, B, first_row, Bmax)));
-        sch_up_B = 0;
-        return MGADMM_OK;
-    }
-
-    // the device table of a solve of B samples on the LDS path: sch_rows x B records
-    int upload_param_schedule(int B) {
-        if (sch_up_B == B && d_sch) return MGADMM_OK;
-        std::vector<LdsSampleParams> rec;
-        ldsparam::fill_records(wt.source(true, p), p.ablation, B, rec);
-        MG_TRY(grow(d_sch, sch_elems, rec.size()));
-        MG_HIP(hipMemcpy(d_sch, rec.data(), sizeof(LdsSampleParams) * rec.size(), hipMemcpyHostToDevice));
-        sch_up_B = B;
-        return MGADMM_OK;
+        return refused(wt.set_schedule(sch, n_rows, B, first_row, Bmax));
     }
 
     // ---------------------------------------------------------------- adaptive penalties
     // Residual balancing of rho, rho_u, rho_d per sample (lds_adapt.h) in the solves that follow; `start`: iterations the
     // problem has run already (a resumed solve continues the periods).  nullptr clears
     int set_adaptive_rho(const mgadmm_adaptive_rho* ar, int start) override {
-        if (ar == nullptr) {
-            ad_on = false;
-            return MGADMM_OK;
-        }
+        if (ar == nullptr) { ad_on = false; return MGADMM_OK; }
         ldsadapt::Params q;
         q.every = ar->every; q.until = ar->until; q.mu = ar->mu; q.tau = ar->tau;
         q.tau_inv = 1.0 / ar->tau;
@@ -591,32 +504,19 @@ struct Engine : EngineBase {
         return MGADMM_OK;
     }
 
-    // the history of the last solve: rho_hist[p][3][B] = rho, rho_u, rho_d of period p (NaN past a sample's own stop)
-    int get_adaptive_history(int B, double* rho_hist, int max_periods, int* n_periods) override {
+    // periods of the last solve's history (LdsEngine copies the history itself; a streaming solve never adapts)
+    int get_adaptive_history(int, double*, int, int* n_periods) override {
         MG_REQUIRE(n_periods, "get_adaptive_history: n_periods is null");
         *n_periods = ad_last_periods;
-        if (ad_last_periods == 0 || rho_hist == nullptr || max_periods <= 0) return MGADMM_OK;
-        MG_REQUIRE(B == ad_last_B, "get_adaptive_history: the last adaptive_rho solve had B = %d, not %d", ad_last_B, B);
-        MG_HIP(hipSetDevice(g->device));
-        MG_HIP(hipMemcpy(rho_hist, d_ad_hist, sizeof(double) * 3 * (size_t)B * std::min(max_periods, ad_last_periods), hipMemcpyDeviceToHost));
         return MGADMM_OK;
     }
 
     // ---------------------------------------------------------------- per-sample graph weights
-    // Sample b reads the weights of set set_of_sample[b]; every set shares the solver's topology (lds_graph_sets.h plans each
-    // set with the solver's switches and names the first difference).  Synchronous: the old table is freed after the device
-    // has finished whatever read it.  mgadmm_two_loops and the fine-grained entry points keep using the solver's own graph.
+    // Sample b reads the weights of set set_of_sample[b].  The host half: n_sets == 0 clears, the argument checks, the gate;
+    // LdsEngine plans and uploads the sets.  mgadmm_two_loops and the fine-grained entry points keep using the solver's own graph.
     int set_sample_graphs(int n_sets, mgadmm_graph* const* graphs, const int32_t* set_of_sample, int B) override {
         MG_HIP(hipSetDevice(g->device));
-        if (n_sets == 0) {
-            if (d_sg_img) {
-                MG_HIP(hipDeviceSynchronize());
-                (void)hipFree(d_sg_img);
-                d_sg_img = nullptr;
-            }
-            sg_B = sg_sets = 0;
-            return MGADMM_OK;
-        }
+        if (n_sets == 0) { sg_B = 0; return MGADMM_OK; }
         MG_REQUIRE(n_sets >= 1 && graphs && set_of_sample, "set_sample_graphs: n_sets %d needs graphs and set_of_sample", n_sets);
         MG_REQUIRE(B >= 1 && B <= Bmax, "set_sample_graphs: batch %d outside [1, max_batch=%d]", B, Bmax);
         for (int b = 0; b < B; ++b)
@@ -632,35 +532,7 @@ struct Engine : EngineBase {
             MG_REQUIRE(q->reorder == g->reorder && q->has_perm == g->has_perm && q->perm == g->perm,
                        "set_sample_graphs: graphs[%d] has another internal node order than the solver's graph", s);
         }
-        MG_TRY(refused(solvegate::set_sample_graphs_gate(facts(p))));
-        // plan every set (the bank search of a set takes as long as the solver's own: sets are planned side by side)
-        std::vector<ldsplan::Input> sets;
-        for (int s = 0; s < n_sets; ++s)
-            sets.push_back(ldsplan::Input{T, N, false, graphs[s]->transpose_by_gather != 0, graphs[s]->hWu, graphs[s]->hWd, graphs[s]->hWdT});
-        std::vector<int> table;
-        std::string differs;
-        int bad = -1;
-        if (!ldssets::build_table(lds, lds_img_host, sets, lds_sw, table, &bad, differs, std::min(8, (int)std::thread::hardware_concurrency()))) {
-            mg_set_error("set_sample_graphs: sample_graphs set %d does not share the solver's topology -- %s (a weight that underflowed to 0 and "
-                         "was dropped, another k or other neighbour lists?)", bad, differs.c_str());
-            return MGADMM_ERR_UNSUPPORTED;
-        }
-        std::vector<int> set_of((size_t)Bp_max, 0);
-        std::copy(set_of_sample, set_of_sample + B, set_of.begin());
-        int* fresh = nullptr;
-        MG_HIP(hipMalloc(&fresh, sizeof(int) * table.size()));
-        if (hipMemcpy(fresh, table.data(), sizeof(int) * table.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(fresh);
-            mg_set_error("set_sample_graphs: upload of the images failed");
-            return MGADMM_ERR_HIP;
-        }
-        if (!d_sg_set) MG_HIP(hipMalloc(&d_sg_set, sizeof(int) * (size_t)Bp_max));
-        MG_HIP(hipDeviceSynchronize());          // no launch reads the old table any more
-        MG_HIP(hipMemcpy(d_sg_set, set_of.data(), sizeof(int) * set_of.size(), hipMemcpyHostToDevice));
-        if (d_sg_img) (void)hipFree(d_sg_img);
-        d_sg_img = fresh;
-        sg_B = B; sg_sets = n_sets;
-        return MGADMM_OK;
+        return refused(solvegate::set_sample_graphs_gate(facts(p)));
     }
 
     int64_t workspace_bytes() const override { return ws_bytes; }
@@ -1145,13 +1017,17 @@ struct Engine : EngineBase {
         return unpack(q, vec[V_IO1], phi);
     }
 
-    int guess_internal(const Geom& q, const S* ypad, S* x) {
-        // float32 time moments of ADMM.py:772-775
-        float tm = 0, t2m = 0;
+    // float32 time moments of ADMM.py:772-775 over the t_in input steps: the mean of t, and den = the mean of t^2 - tm^2
+    void time_moments(float& tm, float& den) const {
+        float t2m = tm = 0;
         for (int t = 0; t < p.t_in; ++t) { tm += (float)t; t2m += (float)t * (float)t; }
         tm /= (float)p.t_in;
         t2m /= (float)p.t_in;
-        const float den = t2m - tm * tm;
+        den = t2m - tm * tm;
+    }
+    int guess_internal(const Geom& q, const S* ypad, S* x) {
+        float tm, den;
+        time_moments(tm, den);
         dim3 grid((N + 3) / 4, q.Bp / 64);
         hipLaunchKernelGGL((k_initial_guess<S>), grid, dim3(256), 0, st, T, p.t_in, N, q.Bp, (S)tm, (S)den, ypad, x);
         MG_HIP(hipGetLastError());
@@ -1233,12 +1109,12 @@ struct Engine : EngineBase {
 
     // ---------------------------------------------------------------- combined_loop (ADMM.py:511-648)
     // every state tensor the ablation uses must be present in a warm-start state
+    bool has_phi() const { return p.ablation == MGADMM_ABL_NONE || p.ablation == MGADMM_ABL_DGLR; }      // the ablation iterates on (phi, gamma)
+    bool has_zd() const { return p.ablation != MGADMM_ABL_DGLR; }                                        // ... on (zd, gamma_d)
     int check_state_in(const void* x0, const mgadmm_state* si) const {
-        const int abl = p.ablation;
-        const bool has_phi = (abl == MGADMM_ABL_NONE || abl == MGADMM_ABL_DGLR), has_zd = (abl != MGADMM_ABL_DGLR);
         MG_REQUIRE(x0 && si && si->zu && si->gamma_u, "solve_from: x0, state_in.zu and state_in.gamma_u are required");
-        MG_REQUIRE(!has_phi || (si->phi && si->gamma), "solve_from: state_in.phi and state_in.gamma are required for this ablation");
-        MG_REQUIRE(!has_zd || (si->zd && si->gamma_d), "solve_from: state_in.zd and state_in.gamma_d are required for this ablation");
+        MG_REQUIRE(!has_phi() || (si->phi && si->gamma), "solve_from: state_in.phi and state_in.gamma are required for this ablation");
+        MG_REQUIRE(!has_zd() || (si->zd && si->gamma_d), "solve_from: state_in.zd and state_in.gamma_d are required for this ablation");
         return MGADMM_OK;
     }
 
@@ -1275,6 +1151,68 @@ struct Engine : EngineBase {
         return MGADMM_OK;
     }
 
+    // ---- what solve and two_loops share.  Bufs: the workspace vectors that hold the current / next x, zu, zd, phi
+    struct Bufs {
+        int xc = V_XA, xn = V_XB, zuc = V_ZUA, zun = V_ZUB, zdc = V_ZDA, zdn = V_ZDB, phc = V_PHIA, phn = V_PHIB;
+        void swap_inner(bool has_zd) { std::swap(xc, xn); std::swap(zuc, zun); if (has_zd) std::swap(zdc, zdn); }
+    };
+    // packs y (mask mode: T steps, and the mask, returned in *m; prediction mode: t_in steps); `guess`: the first iterate to x
+    int load_input(const Geom& q, const void* y, const void* mask, int mask_f32, bool guess, S* x, const S** m) {
+        MG_TRY(pack(q, y, mask ? T : p.t_in, vec[V_Y]));
+        if (mask) MG_TRY(pack(q, mask, T, vec[V_MASK]));
+        *m = mask ? vec[V_MASK] : nullptr;
+        if (!guess) return MGADMM_OK;
+        return mask ? interp_internal(q, vec[V_Y], *m, mask_f32, x) : guess_internal(q, vec[V_Y], x);
+    }
+    // One inner ADMM step with the weights w = rho, rho_u, rho_d, mu_u, mu_d1, mu_d2: RHS_x, the x, zu and zd CG solves (counts
+    // to it_base[3][Bp]) and the dual updates.  The caller reduces EpiDual's partial norms or not, and swaps the buffers
+    int admm_step(const Geom& q, const double w[6], const Bufs& b, int* it_base, const S* m, bool record, mgadmm_history* hist, int it) {
+        const bool has_phi = this->has_phi(), has_zd = this->has_zd();
+        const S rho = (S)w[0], rho_u = (S)w[1], rho_d = (S)w[2];
+        auto lhs_of = [&](int which) { return lhs_def_of(which, p.ablation, w[0], w[1], w[2], w[3], w[5]); };
+        // ---- RHS_x (ADMM.py:556-564)
+        if (has_phi) {
+            MG_TRY(rows<EpiLin2>(q, op_none(), vec[V_GAM], nullptr, 3, 3, (const S*)vec[b.phc], vec[V_TMP], (S)1, rho));
+            MG_TRY(rows<EpiRhsX>(q, g->op_ldrt(), vec[V_TMP], nullptr, 2, has_zd ? 7 : 5, (const S*)vec[b.zuc],
+                                 (const S*)vec[b.zdc], (const S*)vec[V_GU], (const S*)vec[V_GD], (const S*)vec[V_Y],
+                                 vec[V_RHS], rho_u, rho_d, 1, has_zd ? 1 : 0));
+        } else {
+            MG_TRY(rows<EpiRhsX>(q, op_none(), vec[b.zuc], nullptr, 3, 6, (const S*)vec[b.zuc], (const S*)vec[b.zdc],
+                                 (const S*)vec[V_GU], (const S*)vec[V_GD], (const S*)vec[V_Y], vec[V_RHS], rho_u,
+                                 rho_d, 0, 1));
+        }
+        // ---- x, zu, zd CG solves (ADMM.py:571-592)
+        MG_TRY(cg_internal(q, lhs_of(MGADMM_LHS_X), vec[V_RHS], vec[b.xc], m, vec[b.xn], it_base, record));
+        if (record) MG_TRY(save_coeffs(q.Bp, hist, it, 0, q.B));
+        MG_TRY(rows<EpiLin2>(q, op_none(), vec[V_GU], nullptr, 3, 3, (const S*)vec[b.xn], vec[V_RHS], (S)0.5, (S)(w[1] / 2)));
+        MG_TRY(cg_internal(q, lhs_of(MGADMM_LHS_ZU), vec[V_RHS], vec[b.zuc], nullptr, vec[b.zun], it_base + q.Bp, record));
+        if (record) MG_TRY(save_coeffs(q.Bp, hist, it, 1, q.B));
+        if (has_zd) {
+            MG_TRY(rows<EpiLin2>(q, op_none(), vec[V_GD], nullptr, 3, 3, (const S*)vec[b.xn], vec[V_RHS], (S)0.5, (S)(w[2] / 2)));
+            MG_TRY(cg_internal(q, lhs_of(MGADMM_LHS_ZD), vec[V_RHS], vec[b.zdc], nullptr, vec[b.zdn], it_base + 2 * q.Bp, record));
+            if (record) MG_TRY(save_coeffs(q.Bp, hist, it, 2, q.B));
+        }
+        const S* zd_now = has_zd ? vec[b.zdn] : vec[b.zdc];
+        // ---- dual updates + Laplacian-free residuals (ADMM.py:595-597, 612-636)
+        return rows<EpiDual>(q, op_none(), vec[b.xn], nullptr, 3, has_zd ? 11 : 6, (const S*)vec[b.xc], (const S*)vec[b.zun],
+                             (const S*)vec[b.zuc], zd_now, (const S*)vec[b.zdc], (const S*)vec[V_Y], m, vec[V_GU],
+                             vec[V_GD], rho_u, rho_d, has_zd ? 1 : 0, p.t_in);
+    }
+    // x and the state the caller asked for, in the reference's layout
+    int unpack_results(const Geom& q, const Bufs& b, void* x_out, const mgadmm_state* so) {
+        MG_TRY(unpack(q, vec[b.xc], x_out));
+        if (!so) return MGADMM_OK;
+        void* const phi = has_phi() ? so->phi : nullptr, * const gamma = has_phi() ? so->gamma : nullptr;
+        const std::pair<void*, int> out[] = {{so->zu, b.zuc}, {so->zd, b.zdc}, {phi, b.phc}, {gamma, V_GAM}, {so->gamma_u, V_GU}, {so->gamma_d, V_GD}};
+        for (const auto& o : out) if (o.first) MG_TRY(unpack(q, vec[o.second], o.first));
+        return MGADMM_OK;
+    }
+
+    // one solve on the LDS-resident path: LdsEngine's (lds_engine.h); use_lds() is false for every other engine
+    virtual int solve_lds(const void*, const void*, int, const void*, const mgadmm_state*, void*, const mgadmm_state*, mgadmm_history*) {
+        return MGADMM_ERR_UNSUPPORTED;
+    }
+
     int solve(const void* y, const void* mask, int mask_f32, int B, const void* x0, const mgadmm_state* state_in, void* x_out,
               const mgadmm_state* state_out, mgadmm_history* hist, hipStream_t s) override {
         MG_TRY(check_B(B, "solve"));
@@ -1288,38 +1226,27 @@ struct Engine : EngineBase {
         const Geom q = make_geom(B);
         MG_TRY(ensure_partials(q));
         const size_t ne = velems(q);
-        const int abl = p.ablation;
-        const bool has_phi = (abl == MGADMM_ABL_NONE || abl == MGADMM_ABL_DGLR);
-        const bool has_zd = (abl != MGADMM_ABL_DGLR);
+        const bool has_phi = this->has_phi(), has_zd = this->has_zd();
         const int max_it = p.max_admm_iter;
         const bool record = p.record_cg_coeffs && hist && hist->cg_alpha && hist->cg_beta;
-
         MG_TRY(ensure_hist_ps(hist, B));
         MG_HIP(hipMemsetAsync(d_nonfinite, 0, sizeof(int), st));
         MG_HIP(hipMemsetAsync(d_ps, 0, sizeof(double) * MGADMM_NMETRIC * q.Bp, st));
         MG_HIP(hipMemsetAsync(d_cg_iters, 0, sizeof(int) * (size_t)max_it * 3 * q.Bp, st));
 
-        int xc = V_XA, xn = V_XB, zuc = V_ZUA, zun = V_ZUB, zdc = V_ZDA, zdn = V_ZDB, phc = V_PHIA, phn = V_PHIB;
+        Bufs b;
         const S* m = nullptr;
-        if (mask) {
-            MG_TRY(pack(q, y, T, vec[V_Y]));
-            MG_TRY(pack(q, mask, T, vec[V_MASK]));
-            m = vec[V_MASK];
-            if (!state_in) MG_TRY(interp_internal(q, vec[V_Y], m, mask_f32, vec[xc]));
-        } else {
-            MG_TRY(pack(q, y, p.t_in, vec[V_Y]));
-            if (!state_in) MG_TRY(guess_internal(q, vec[V_Y], vec[xc]));
-        }
+        MG_TRY(load_input(q, y, mask, mask_f32, !state_in, vec[b.xc], &m));      // (a warm start brings its own x)
         if (state_in) {                       // warm start: the saved state replaces ADMM.py:529-544
-            MG_TRY(pack(q, x0, T, vec[xc]));
-            MG_TRY(pack(q, state_in->zu, T, vec[zuc]));
+            MG_TRY(pack(q, x0, T, vec[b.xc]));
+            MG_TRY(pack(q, state_in->zu, T, vec[b.zuc]));
             MG_TRY(pack(q, state_in->gamma_u, T, vec[V_GU]));
             if (has_zd) {
-                MG_TRY(pack(q, state_in->zd, T, vec[zdc]));
+                MG_TRY(pack(q, state_in->zd, T, vec[b.zdc]));
                 MG_TRY(pack(q, state_in->gamma_d, T, vec[V_GD]));
             }
             if (has_phi) {
-                MG_TRY(pack(q, state_in->phi, T, vec[phc]));
+                MG_TRY(pack(q, state_in->phi, T, vec[b.phc]));
                 MG_TRY(pack(q, state_in->gamma, T, vec[V_GAM]));
             }
         } else {
@@ -1327,10 +1254,10 @@ struct Engine : EngineBase {
             MG_TRY(fill(vec[V_GD], ne, (S)0.1));
             if (has_phi) {
                 MG_TRY(fill(vec[V_GAM], ne, (S)0.1));
-                MG_TRY(op_store(q, g->op_ldr(), vec[xc], vec[phc]));
+                MG_TRY(op_store(q, g->op_ldr(), vec[b.xc], vec[b.phc]));
             }
-            MG_HIP(hipMemcpyAsync(vec[zuc], vec[xc], ne * sizeof(S), hipMemcpyDeviceToDevice, st));
-            MG_HIP(hipMemcpyAsync(vec[zdc], vec[xc], ne * sizeof(S), hipMemcpyDeviceToDevice, st));
+            MG_HIP(hipMemcpyAsync(vec[b.zuc], vec[b.xc], ne * sizeof(S), hipMemcpyDeviceToDevice, st));
+            MG_HIP(hipMemcpyAsync(vec[b.zdc], vec[b.xc], ne * sizeof(S), hipMemcpyDeviceToDevice, st));
         }
 
         // the six weights of an iteration: the row of the schedule (the shared form: solve_gate let no other through) or the scalars of `p`
@@ -1340,67 +1267,28 @@ struct Engine : EngineBase {
         for (int it = 0; it < max_it; ++it) {
             double w[6];
             ldsparam::row_weights(wsrc, it, wt.sch_row0, w);
-            const S rho = (S)w[0], rho_u = (S)w[1], rho_d = (S)w[2];
-            auto lhs_of = [&](int which) { return lhs_def_of(which, p.ablation, w[0], w[1], w[2], w[3], w[5]); };
-            // ---- RHS_x (ADMM.py:556-564)
-            if (has_phi) {
-                MG_TRY(rows<EpiLin2>(q, op_none(), vec[V_GAM], nullptr, 3, 3, (const S*)vec[phc], vec[V_TMP], (S)1, rho));
-                MG_TRY(rows<EpiRhsX>(q, g->op_ldrt(), vec[V_TMP], nullptr, 2, has_zd ? 7 : 5, (const S*)vec[zuc],
-                                     (const S*)vec[zdc], (const S*)vec[V_GU], (const S*)vec[V_GD], (const S*)vec[V_Y],
-                                     vec[V_RHS], rho_u, rho_d, 1, has_zd ? 1 : 0));
-            } else {
-                MG_TRY(rows<EpiRhsX>(q, op_none(), vec[zuc], nullptr, 3, 6, (const S*)vec[zuc], (const S*)vec[zdc],
-                                     (const S*)vec[V_GU], (const S*)vec[V_GD], (const S*)vec[V_Y], vec[V_RHS], rho_u,
-                                     rho_d, 0, 1));
-            }
-            // ---- x, zu, zd CG solves (ADMM.py:571-592)
-            int* it_base = d_cg_iters + (size_t)it * 3 * q.Bp;
-            MG_TRY(cg_internal(q, lhs_of(MGADMM_LHS_X), vec[V_RHS], vec[xc], m, vec[xn], it_base, record));
-            if (record) MG_TRY(save_coeffs(q, hist, it, 0, B));
-            MG_TRY(rows<EpiLin2>(q, op_none(), vec[V_GU], nullptr, 3, 3, (const S*)vec[xn], vec[V_RHS], (S)0.5, (S)(w[1] / 2)));
-            MG_TRY(cg_internal(q, lhs_of(MGADMM_LHS_ZU), vec[V_RHS], vec[zuc], nullptr, vec[zun], it_base + q.Bp, record));
-            if (record) MG_TRY(save_coeffs(q, hist, it, 1, B));
-            if (has_zd) {
-                MG_TRY(rows<EpiLin2>(q, op_none(), vec[V_GD], nullptr, 3, 3, (const S*)vec[xn], vec[V_RHS], (S)0.5, (S)(w[2] / 2)));
-                MG_TRY(cg_internal(q, lhs_of(MGADMM_LHS_ZD), vec[V_RHS], vec[zdc], nullptr, vec[zdn], it_base + 2 * q.Bp, record));
-                if (record) MG_TRY(save_coeffs(q, hist, it, 2, B));
-            }
-            const S* zd_now = has_zd ? vec[zdn] : vec[zdc];
-            // ---- dual updates + Laplacian-free residuals (ADMM.py:595-597, 612-636)
-            MG_TRY(rows<EpiDual>(q, op_none(), vec[xn], nullptr, 3, has_zd ? 11 : 6, (const S*)vec[xc], (const S*)vec[zun],
-                                 (const S*)vec[zuc], zd_now, (const S*)vec[zdc], (const S*)vec[V_Y], m, vec[V_GU],
-                                 vec[V_GD], rho_u, rho_d, has_zd ? 1 : 0, p.t_in));
-            {
-                FinMetrics<6> f{d_ps, q.Bp, {MGADMM_M_XSHIFT, MGADMM_M_PRI_ZU, MGADMM_M_DUAL_ZU, has_zd ? MGADMM_M_PRI_ZD : -1,
-                                            has_zd ? MGADMM_M_DUAL_ZD : -1, MGADMM_M_RECOVER}};
-                MG_TRY((reduce<6>(q, f, nullptr)));
-            }
+            const S rho = (S)w[0];
+            MG_TRY(admm_step(q, w, b, d_cg_iters + (size_t)it * 3 * q.Bp, m, record, hist, it));
+            MG_TRY((reduce<6>(q, FinMetrics<6>{d_ps, q.Bp, {MGADMM_M_XSHIFT, MGADMM_M_PRI_ZU, MGADMM_M_DUAL_ZU, has_zd ? MGADMM_M_PRI_ZD : -1,
+                                                       has_zd ? MGADMM_M_DUAL_ZD : -1, MGADMM_M_RECOVER}}, nullptr)));
             // ---- phi prox, gamma update, Ldr-based residuals and regularisers (ADMM.py:600-606, 627-637)
-            MG_TRY(rows<EpiPhi>(q, g->op_ldr(), vec[xn], nullptr, 2, has_phi ? 5 : 1, (const S*)vec[phc], vec[phn], vec[V_GAM],
+            MG_TRY(rows<EpiPhi>(q, g->op_ldr(), vec[b.xn], nullptr, 2, has_phi ? 5 : 1, (const S*)vec[b.phc], vec[b.phn], vec[V_GAM],
                                 rho, (S)(w[4] / w[0]), has_phi ? 1 : 0));
-            {
-                FinMetrics<4> f{d_ps, q.Bp, {has_phi ? MGADMM_M_PRI_PHI : -1, has_phi ? MGADMM_M_DUAL_PHI : -1,
-                                            has_phi ? MGADMM_M_DGTV : -1, has_zd ? MGADMM_M_DGLR : -1}};
-                MG_TRY((reduce<4>(q, f, nullptr)));
-            }
-            MG_TRY(rows<EpiDot>(q, g->op_lu(), vec[xn], nullptr, 2, 1));
-            {
-                FinMetrics<1> f{d_ps, q.Bp, {MGADMM_M_GLR}};
-                MG_TRY((reduce<1>(q, f, nullptr)));
-            }
+            MG_TRY((reduce<4>(q, FinMetrics<4>{d_ps, q.Bp, {has_phi ? MGADMM_M_PRI_PHI : -1, has_phi ? MGADMM_M_DUAL_PHI : -1,
+                                                       has_phi ? MGADMM_M_DGTV : -1, has_zd ? MGADMM_M_DGLR : -1}}, nullptr)));
+            MG_TRY(rows<EpiDot>(q, g->op_lu(), vec[b.xn], nullptr, 2, 1));
+            MG_TRY((reduce<1>(q, FinMetrics<1>{d_ps, q.Bp, {MGADMM_M_GLR}}, nullptr)));
             const int nbk = (N + 63) / 64;
-            hipLaunchKernelGGL((k_dxps<S>), dim3(T * nbk), dim3(256), 0, st, T, N, q.Bp, B, nbk, (const S*)vec[xn],
-                               (const S*)vec[xc], d_dxpart);
+            hipLaunchKernelGGL((k_dxps<S>), dim3(T * nbk), dim3(256), 0, st, T, N, q.Bp, B, nbk, (const S*)vec[b.xn],
+                               (const S*)vec[b.xc], d_dxpart);
             hipLaunchKernelGGL(k_dxps_final, dim3((T + 63) / 64), dim3(64), 0, st, T, nbk, (const double*)d_dxpart,
                                d_dxps + (size_t)it * T);
             hipLaunchKernelGGL(k_batch_metrics, dim3(MGADMM_NMETRIC), dim3(256), 0, st, (const double*)d_ps, q.Bp, B,
                                d_hist + (size_t)it * MGADMM_NMETRIC,
                                (hist && hist->metrics_per_sample) ? d_hist_ps + (size_t)it * MGADMM_NMETRIC * B : nullptr);
             MG_HIP(hipGetLastError());
-            std::swap(xc, xn);
-            std::swap(zuc, zun);
-            if (has_zd) std::swap(zdc, zdn);
-            if (has_phi) std::swap(phc, phn);
+            b.swap_inner(has_zd);
+            if (has_phi) std::swap(b.phc, b.phn);
             n_done = it + 1;
             if (p.check_stop) {
                 bool stop = false;
@@ -1408,16 +1296,7 @@ struct Engine : EngineBase {
                 if (stop) break;
             }
         }
-        // ---- results
-        MG_TRY(unpack(q, vec[xc], x_out));
-        if (state_out) {
-            if (state_out->zu) MG_TRY(unpack(q, vec[zuc], state_out->zu));
-            if (state_out->zd) MG_TRY(unpack(q, vec[zdc], state_out->zd));
-            if (state_out->phi && has_phi) MG_TRY(unpack(q, vec[phc], state_out->phi));
-            if (state_out->gamma && has_phi) MG_TRY(unpack(q, vec[V_GAM], state_out->gamma));
-            if (state_out->gamma_u) MG_TRY(unpack(q, vec[V_GU], state_out->gamma_u));
-            if (state_out->gamma_d) MG_TRY(unpack(q, vec[V_GD], state_out->gamma_d));
-        }
+        MG_TRY(unpack_results(q, b, x_out, state_out));
         return finish_history(hist, n_done, B, q.Bp, rc_final);
     }
 
@@ -1434,9 +1313,7 @@ struct Engine : EngineBase {
         const Geom q = make_geom(B);
         MG_TRY(ensure_partials(q));
         const size_t ne = velems(q);
-        const int abl = p.ablation;
-        const bool has_phi = (abl == MGADMM_ABL_NONE || abl == MGADMM_ABL_DGLR);
-        const bool has_zd = (abl != MGADMM_ABL_DGLR);
+        const bool has_phi = this->has_phi(), has_zd = this->has_zd();
         const int n_outer = p.max_admm_iter, n_inner = p.max_inner_iter;
         const size_t rows_needed = (size_t)n_outer * n_inner;
         if (rows_needed > (size_t)max_admm_alloc) {          // d_cg_iters holds one row of 3 x Bp counts per inner iteration
@@ -1465,80 +1342,36 @@ struct Engine : EngineBase {
         MG_HIP(hipMemsetAsync(d_nonfinite, 0, sizeof(int), st));
         MG_HIP(hipMemsetAsync(d_ps, 0, sizeof(double) * MGADMM_NMETRIC * q.Bp, st));
         MG_HIP(hipMemsetAsync(d_cg_iters, 0, sizeof(int) * rows_needed * 3 * q.Bp, st));
-        int xc = V_XA, xn = V_XB, zuc = V_ZUA, zun = V_ZUB, zdc = V_ZDA, zdn = V_ZDB, phc = V_PHIA, phn = V_PHIB;
+        Bufs b;
         const S* m = nullptr;
-        if (mask) {
-            MG_TRY(pack(q, y, T, vec[V_Y]));
-            MG_TRY(pack(q, mask, T, vec[V_MASK]));
-            m = vec[V_MASK];
-            MG_TRY(interp_internal(q, vec[V_Y], m, mask_f32, vec[xc]));
-        } else {
-            MG_TRY(pack(q, y, p.t_in, vec[V_Y]));
-            MG_TRY(guess_internal(q, vec[V_Y], vec[xc]));
-        }
+        MG_TRY(load_input(q, y, mask, mask_f32, true, vec[b.xc], &m));
         if (has_phi) {
             MG_TRY(fill(vec[V_GAM], ne, (S)0.1));
-            MG_TRY(op_store(q, g->op_ldr(), vec[xc], vec[phc]));
+            MG_TRY(op_store(q, g->op_ldr(), vec[b.xc], vec[b.phc]));
         }
-        const S rho = (S)p.rho, rho_u = (S)p.rho_u, rho_d = (S)p.rho_d;
+        const double w[6] = {p.rho, p.rho_u, p.rho_d, p.mu_u, p.mu_d1, p.mu_d2};      // the scalars: a schedule is not read here
         int n_done = 0;
         for (int o = 0; o < n_outer; ++o) {
             MG_TRY(fill(vec[V_GU], ne, (S)0.1));
             MG_TRY(fill(vec[V_GD], ne, (S)0.1));
-            MG_HIP(hipMemcpyAsync(vec[zuc], vec[xc], ne * sizeof(S), hipMemcpyDeviceToDevice, st));
-            MG_HIP(hipMemcpyAsync(vec[zdc], vec[xc], ne * sizeof(S), hipMemcpyDeviceToDevice, st));
+            MG_HIP(hipMemcpyAsync(vec[b.zuc], vec[b.xc], ne * sizeof(S), hipMemcpyDeviceToDevice, st));
+            MG_HIP(hipMemcpyAsync(vec[b.zdc], vec[b.xc], ne * sizeof(S), hipMemcpyDeviceToDevice, st));
             for (int in = 0; in < n_inner; ++in) {
-                if (has_phi) {
-                    MG_TRY(rows<EpiLin2>(q, op_none(), vec[V_GAM], nullptr, 3, 3, (const S*)vec[phc], vec[V_TMP], (S)1, rho));
-                    MG_TRY(rows<EpiRhsX>(q, g->op_ldrt(), vec[V_TMP], nullptr, 2, has_zd ? 7 : 5, (const S*)vec[zuc],
-                                         (const S*)vec[zdc], (const S*)vec[V_GU], (const S*)vec[V_GD], (const S*)vec[V_Y],
-                                         vec[V_RHS], rho_u, rho_d, 1, has_zd ? 1 : 0));
-                } else {
-                    MG_TRY(rows<EpiRhsX>(q, op_none(), vec[zuc], nullptr, 3, 6, (const S*)vec[zuc], (const S*)vec[zdc],
-                                         (const S*)vec[V_GU], (const S*)vec[V_GD], (const S*)vec[V_Y], vec[V_RHS], rho_u,
-                                         rho_d, 0, 1));
-                }
-                int* it_base = d_cg_iters + ((size_t)o * n_inner + in) * 3 * q.Bp;
-                MG_TRY(cg_internal(q, lhs_def(MGADMM_LHS_X), vec[V_RHS], vec[xc], m, vec[xn], it_base, false));
-                MG_TRY(rows<EpiLin2>(q, op_none(), vec[V_GU], nullptr, 3, 3, (const S*)vec[xn], vec[V_RHS], (S)0.5, (S)(p.rho_u / 2)));
-                MG_TRY(cg_internal(q, lhs_def(MGADMM_LHS_ZU), vec[V_RHS], vec[zuc], nullptr, vec[zun], it_base + q.Bp, false));
-                if (has_zd) {
-                    MG_TRY(rows<EpiLin2>(q, op_none(), vec[V_GD], nullptr, 3, 3, (const S*)vec[xn], vec[V_RHS], (S)0.5, (S)(p.rho_d / 2)));
-                    MG_TRY(cg_internal(q, lhs_def(MGADMM_LHS_ZD), vec[V_RHS], vec[zdc], nullptr, vec[zdn], it_base + 2 * q.Bp, false));
-                }
-                const S* zd_now = has_zd ? vec[zdn] : vec[zdc];
-                // gamma_u += rho_u (x - zu), gamma_d += rho_d (x - zd)   (ADMM.py:488-490); the fused norms are not kept
-                MG_TRY(rows<EpiDual>(q, op_none(), vec[xn], nullptr, 3, has_zd ? 11 : 6, (const S*)vec[xc], (const S*)vec[zun],
-                                     (const S*)vec[zuc], zd_now, (const S*)vec[zdc], (const S*)vec[V_Y], m, vec[V_GU],
-                                     vec[V_GD], rho_u, rho_d, has_zd ? 1 : 0, p.t_in));
-                std::swap(xc, xn);
-                std::swap(zuc, zun);
-                if (has_zd) std::swap(zdc, zdn);
+                // (no CG coefficients are recorded and EpiDual's fused norms are not kept: ADMM.py:488-490)
+                MG_TRY(admm_step(q, w, b, d_cg_iters + ((size_t)o * n_inner + in) * 3 * q.Bp, m, false, nullptr, 0));
+                b.swap_inner(has_zd);
             }
             if (has_phi) {          // phi = phi_direct(x, gamma); gamma += rho (phi - Ldr x)   (ADMM.py:497-504)
-                MG_TRY(rows<EpiPhi>(q, g->op_ldr(), vec[xc], nullptr, 2, 5, (const S*)vec[phc], vec[phn], vec[V_GAM], rho,
+                MG_TRY(rows<EpiPhi>(q, g->op_ldr(), vec[b.xc], nullptr, 2, 5, (const S*)vec[b.phc], vec[b.phn], vec[V_GAM], (S)p.rho,
                                     (S)(p.mu_d1 / p.rho), 1));
-                std::swap(phc, phn);
+                std::swap(b.phc, b.phn);
             }
             n_done = o + 1;
         }
-        MG_TRY(unpack(q, vec[xc], x_out));
-        if (state_out) {
-            if (state_out->zu) MG_TRY(unpack(q, vec[zuc], state_out->zu));
-            if (state_out->zd) MG_TRY(unpack(q, vec[zdc], state_out->zd));
-            if (state_out->phi && has_phi) MG_TRY(unpack(q, vec[phc], state_out->phi));
-            if (state_out->gamma && has_phi) MG_TRY(unpack(q, vec[V_GAM], state_out->gamma));
-            if (state_out->gamma_u) MG_TRY(unpack(q, vec[V_GU], state_out->gamma_u));
-            if (state_out->gamma_d) MG_TRY(unpack(q, vec[V_GD], state_out->gamma_d));
-        }
+        MG_TRY(unpack_results(q, b, x_out, state_out));
         if (hist) {
             hist->n_iters = n_done;
-            if (hist->cg_iters) {
-                std::vector<int> tmp(rows_needed * 3 * q.Bp);
-                MG_HIP(hipMemcpyAsync(tmp.data(), d_cg_iters, sizeof(int) * tmp.size(), hipMemcpyDeviceToHost, st));
-                MG_HIP(hipStreamSynchronize(st));
-                for (size_t r = 0; r < rows_needed * 3; ++r) memcpy(hist->cg_iters + r * B, tmp.data() + r * q.Bp, sizeof(int) * B);
-            }
+            if (hist->cg_iters) MG_TRY(fetch_cg_iters(hist->cg_iters, rows_needed, B, q.Bp));
         }
         MG_HIP(hipMemcpyAsync(h_flag, d_nonfinite, sizeof(int), hipMemcpyDeviceToHost, st));
         MG_HIP(hipStreamSynchronize(st));
@@ -1549,398 +1382,14 @@ struct Engine : EngineBase {
         return MGADMM_OK;
     }
 
-    // ---------------------------------------------------------------- LDS-resident fused path
-    int plan_lds() {
-        lds = LdsPlan();
-        if (hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess) { (void)hipGetLastError(); dev_cus = 0; }
-        if (!std::is_same<S, float>::value) return MGADMM_OK;
-        // which k_admm_lds instance, its geometry and the image of its tables: plain host code, lds_plan.h
-        std::vector<int> img;
-        const ldsplan::Input in{T, N, g->mode == MGADMM_TEMPORAL_BAND, g->transpose_by_gather != 0, g->hWu, g->hWd, g->hWdT};
-        lds_sw = ldsplan::Switches::from_env();
-        const ldsplan::Status planned = ldsplan::make(in, lds_sw, lds, img);
-        if (planned == ldsplan::ROWS_DO_NOT_FIT) {
-            mg_set_error("lds: row plan does not fit its launch word (%d waves)", lds.block / 64);
-            return MGADMM_ERR_INVALID;
-        }
-        if (planned == ldsplan::NO_PLAN) return MGADMM_OK;
-        MG_HIP(hipMalloc(&d_lds_csr, sizeof(int) * img.size()));
-        MG_HIP(hipMemcpy(d_lds_csr, img.data(), sizeof(int) * img.size(), hipMemcpyHostToDevice));
-        lds_img_host = img;
-        MG_HIP(hipMalloc(&d_m2, sizeof(double) * T * N * (1 + (size_t)(Bmax + 63) / 64)));
-        MG_HIP(hipMalloc(&d_stop, sizeof(int)));
-        MG_HIP(hipMemset(d_stop, 0, sizeof(int)));
-        MG_HIP(hipMalloc(&d_ps_ring, sizeof(double) * LDS_SETS * LDS_MAXJ * MGADMM_NMETRIC * Bp_max));
-        MG_HIP(hipMalloc(&d_pstop, sizeof(int) * (2 * (size_t)Bp_max + 1)));
-        {
-            // helper stream of the overlapped outer loop: non-blocking (the caller's stream may be the legacy default stream,
-            // which would serialise a blocking stream with itself), lowest priority (the k_admm_lds workgroups of the next
-            // iteration take the CUs first; the one-wave workgroups of the metric kernels fill the room they leave)
-            int lo = 0, hi = 0;
-            MG_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-            if (const char* e = getenv("MGADMM_LDS_SIDE_PRIO")) lo = atoi(e) > 0 ? hi : lo;
-            MG_HIP(hipStreamCreateWithPriority(&st_side, hipStreamNonBlocking, lo));
-            for (auto& e : ev_main) MG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            for (auto& e : ev_side) MG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        return MGADMM_OK;
-    }
-
-    // row_of_node on the device for the kernels that convert between node order and the thread-major state (nullptr: identity)
-    const int* lds_row_of_node() const { return lds.row_order ? d_lds_csr + lds.off_rown : nullptr; }
-
-    int launch_lds(const LdsArgs& a, int B) {
-        const bool timed = prof_open(0, 0.0);
-        LdsLaunch L{lds.instance, lds.block, lds.lds_bytes, &lds_instance, &lds_unit};
-        const int rc = mg_lds_iteration(L, a, B, st);
-        if (timed) prof_close();
-        return rc;
-    }
-
-    // ---------------------------------------------------------------- solve_lds: one solve on the LDS path
-    struct LdsRun {                       // what the members below share
-        ldssched::Schedule s;
-        LdsArgs a;
-        int B, Bp;
-        bool has_phi, has_zd, record, cold;   // cold: no warm-start state
-        float* xo;                        // the caller's x_out
-        mgadmm_history* hist;
-        int n_done = 0, rc = MGADMM_OK;
-        std::vector<int> ad_bounds;       // adaptive penalties: iterations done at every step enqueued so far
-    };
-
-    // buffer of an iterate slot; slots beyond the workspace vectors are allocated here
-    int lds_ring_reserve(int slots) {
-        while (NRING + (int)lds_ring_extra.size() < slots) {
-            float* b = nullptr;
-            MG_HIP(hipMalloc(&b, vec_elems * sizeof(S)));
-            lds_ring_extra.push_back(b);
-            ws_bytes += (int64_t)(vec_elems * sizeof(S));
-        }
-        return MGADMM_OK;
-    }
-    float* lds_ring(int slot) const { return slot < NRING ? (float*)vec[ring_ids[slot]] : lds_ring_extra[slot - NRING]; }
-    // iterate k (k = 0: the initial guess)
-    float* lds_xbuf(const LdsRun& r, int k) const {
-        const int slot = r.s.slot_of_iterate(k);
-        return slot == ldssched::X_OUT ? r.xo : lds_ring(slot);
-    }
-
-    // the part of the launch arguments that no schedule changes.  zu, zd, phi and the dual variables: workspace vectors in the
-    // kernel's thread-major layout (lds_kernels.h, lds_state_index)
-    void lds_fill_args(LdsRun& r, const void* y, const void* mask) const {
-        LdsArgs& a = r.a;
-        a = LdsArgs{};
-        a.T = T; a.N = N; a.TN = T * N; a.TS = lds.TS; a.t_in = p.t_in; a.G = lds.G; a.B = r.B; a.Bp = r.Bp;
-        a.nthreads = lds.nthreads; a.NR = lds.NR; a.tail_pairs = lds.tail_pairs;
-        a.has_phi = r.has_phi; a.has_zd = r.has_zd;
-        const LhsDef dx = lhs_def(MGADMM_LHS_X);
-        a.lhsx_kind = dx.kind == 1 ? 1 : 0;
-        a.cx1 = (float)dx.c1; a.cx2 = (float)dx.c2;
-        a.band = g->mode == MGADMM_TEMPORAL_BAND; a.skip = g->skip;
-        a.q1 = a.band ? 0 : g->q1;
-        a.max_cg = p.max_cg_iter; a.record = r.record ? 1 : 0;
-        a.rho = (float)p.rho; a.rho_u = (float)p.rho_u; a.rho_d = (float)p.rho_d;
-        a.mu_u = (float)p.mu_u; a.mu_d1 = (float)p.mu_d1; a.mu_d2 = (float)p.mu_d2;
-        a.cg_tol2 = p.cg_tol * p.cg_tol;
-        a.csr = d_lds_csr; a.lds_img0 = lds.lds_img0; a.lds_img_ints = lds.lds_img_ints;
-        a.off_rp_u = lds.off_rp_u; a.off_rp_d = lds.off_rp_d;
-        a.off_en_u = lds.off_en_u; a.off_en_d = lds.off_en_d; a.off_lead_t = lds.off_lead_t; a.off_tail_t = lds.off_tail_t; a.off_diag = lds.off_diag;
-        a.npos = lds.npos_word; a.off_node = lds.off_node;
-        a.band_w = g->band_w;
-        a.zu = (float*)vec[V_ZUA]; a.zd = (float*)vec[V_ZDA]; a.phi = (float*)vec[V_PHIA];
-        a.gam = (float*)vec[V_GAM]; a.gu = (float*)vec[V_GU]; a.gd = (float*)vec[V_GD];
-        // staggered start (k_admm_lds): only when the launch runs several rounds of workgroups per CU
-        const int ncu = dev_cus > 0 ? dev_cus : 256;
-        int us = 48;
-        if (const char* e = getenv("MGADMM_LDS_STAGGER_US")) us = atoi(e);
-        a.stagger_wgs = ncu;
-        a.stagger_ticks = (r.B >= 2 * ncu && us > 0) ? us * 100 : 0;
-        a.y = (const float*)y; a.mask = (const float*)mask;
-        a.alpha_hist = r.record ? (float*)d_alpha_hist : nullptr; a.beta_hist = r.record ? (float*)d_beta_hist : nullptr;
-        a.nonfinite = d_nonfinite;
-    }
-
-    // iterate 0 and the state: a warm start is converted into the thread-major layout, a cold start forms ADMM.py:528-544
-    int lds_state_in(const LdsRun& r, const void* x0, const mgadmm_state* si) {
-        const LdsArgs& a = r.a;
-        float* const x = lds_xbuf(r, 0);
-        if (!si) {
-            float tm = 0, t2m = 0;
-            for (int t = 0; t < p.t_in; ++t) { tm += (float)t; t2m += (float)t * (float)t; }
-            tm /= (float)p.t_in;
-            t2m /= (float)p.t_in;
-            const float den = t2m - tm * tm;
-            return mg_lds_init(a.mask != nullptr, T, p.t_in, N, lds.TPG, r.B, tm, den, a.y, a.mask, x, a.zu, a.zd, a.gam, a.gu, a.gd,
-                               d_nonfinite, lds_row_of_node(), st);
-        }
-        if (x0 != nullptr && x != x0) MG_HIP(hipMemcpyAsync(x, x0, (size_t)r.B * T * N * sizeof(float), hipMemcpyDeviceToDevice, st));
-        auto in = [&](float* dst, const void* src) {
-            return src == nullptr ? (int)MGADMM_OK : mg_lds_state_layout(true, T, N, lds.TPG, r.B, (const float*)src, dst, lds_row_of_node(), st);
-        };
-        MG_TRY(in(a.zu, si->zu));
-        MG_TRY(in(a.gu, si->gamma_u));
-        MG_TRY(in(a.zd, si->zd));            // the vectors an ablation does not iterate on are carried through
-        MG_TRY(in(a.gd, si->gamma_d));
-        MG_TRY(in(a.phi, si->phi));
-        return in(a.gam, si->gamma);
-    }
-    // the state the caller asked for, in the reference's layout
-    int lds_state_out(const LdsRun& r, const mgadmm_state* so) {
-        const LdsArgs& a = r.a;
-        auto out = [&](void* dst, const float* src) {
-            return dst == nullptr ? (int)MGADMM_OK : mg_lds_state_layout(false, T, N, lds.TPG, r.B, src, (float*)dst, lds_row_of_node(), st);
-        };
-        MG_TRY(out(so->zu, a.zu));
-        MG_TRY(out(so->zd, a.zd));
-        if (r.has_phi) {
-            MG_TRY(out(so->phi, a.phi));
-            MG_TRY(out(so->gamma, a.gam));
-        }
-        MG_TRY(out(so->gamma_u, a.gu));
-        return out(so->gamma_d, a.gd);
-    }
-
-    // the whole-batch metrics of iteration `it` (delta_x_per_step, norms / means over the samples) on stream `s`
-    int lds_batch_metrics(const LdsRun& r, int it, const double* ps, hipStream_t s) {
-        const bool per_sample = r.hist && r.hist->metrics_per_sample;
-        MG_TRY(mg_lds_dxps(T, N, r.B, (const float*)lds_xbuf(r, it + 1), (const float*)lds_xbuf(r, it), d_m2, d_dxps + (size_t)it * T, r.a.stop, s));
-        hipLaunchKernelGGL(k_batch_metrics, dim3(MGADMM_NMETRIC), dim3(256), 0, s, ps, r.Bp, r.B, d_hist + (size_t)it * MGADMM_NMETRIC,
-                           per_sample ? d_hist_ps + (size_t)it * MGADMM_NMETRIC * r.B : nullptr);
-        MG_HIP(hipGetLastError());
-        return MGADMM_OK;
-    }
-
-    // The host's late look at a device word (the stop word, the number of stopped samples): after step `c` the word is copied
-    // to the pinned ring, and *word is what it was after step c - LAG (0 while there is no such step): ldssched::lag_step
-    int lagged_word(int c, const int* d_word, int* word) {
-        const ldssched::LagStep l = ldssched::lag_step(c, LAG);
-        MG_HIP(hipMemcpyAsync(h_flag + 1 + l.put, d_word, sizeof(int), hipMemcpyDeviceToHost, st));
-        MG_HIP(hipEventRecord(ev_ring[l.put], st));
-        *word = 0;
-        if (l.get >= 0) {
-            MG_HIP(hipEventSynchronize(ev_ring[l.get]));
-            *word = h_flag[1 + l.get];
-        }
-        return MGADMM_OK;
-    }
-
-    // Adaptive penalties, start of a solve: every row of the table holds the records of the start weights (the per-sample
-    // table where one is set, otherwise the scalars), period 0 of the history the start penalties, the later periods NaN
-    int adapt_begin(LdsRun& r) {
-        const int B = r.B, max_it = r.s.max_it;
-        const ldsparam::Source src = wt.source(false, p);
-        std::vector<LdsSampleParams> row, rec;
-        ldsparam::fill_records(src, p.ablation, B, row);      // (one row: no schedule)
-        rec.reserve((size_t)max_it * B);
-        for (int k = 0; k < max_it; ++k) rec.insert(rec.end(), row.begin(), row.end());
-        std::vector<double> w((size_t)ldsparam::NW * B);
-        for (int f = 0; f < ldsparam::NW; ++f)
-            for (int b = 0; b < B; ++b) w[(size_t)f * B + b] = ldsparam::weight_of(src, f, 0, b);
-        const size_t hist_rows = (size_t)max_it / ad.every + 2;
-        MG_TRY(grow(d_ad_tab, ad_tab_elems, rec.size()));
-        MG_TRY(grow(d_ad_w, ad_w_elems, w.size()));
-        MG_TRY(grow(d_ad_hist, ad_hist_elems, hist_rows * 3 * B));
-        MG_HIP(hipMemcpy(d_ad_tab, rec.data(), sizeof(LdsSampleParams) * rec.size(), hipMemcpyHostToDevice));
-        MG_HIP(hipMemcpy(d_ad_w, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice));
-        MG_HIP(hipMemcpy(d_ad_hist, w.data(), sizeof(double) * 3 * B, hipMemcpyHostToDevice));
-        MG_HIP(hipMemsetAsync(d_ad_hist + (size_t)3 * B, 0xFF, sizeof(double) * (hist_rows - 1) * 3 * B, st));      // (all bits set: a NaN)
-        ad_last_B = B;
-        return MGADMM_OK;
-    }
-    // after the launch whose last iteration is `it`: the step, if one follows that iteration (ldsadapt::step_after), on the
-    // caller's stream; ps = the per-sample sums [NMETRIC][Bp] of iteration `it`
-    int adapt_step(LdsRun& r, int it, const double* ps) {
-        if (!ad_on || !ldsadapt::step_after(it, ad_start, ad.every, ad.until)) return MGADMM_OK;
-        const ldsadapt::Rows rows = ldsadapt::rows_after(it, ad_start, ad.every, ad.until, r.s.max_it);
-        r.ad_bounds.push_back(it + 1);
-        LdsAdaptArgs k;
-        k.ps = ps; k.pstop = r.a.pstop; k.w = d_ad_w; k.table = d_ad_tab;
-        k.hist = d_ad_hist + r.ad_bounds.size() * 3 * (size_t)r.B;
-        k.B = r.B; k.Bp = r.Bp; k.row_first = rows.first; k.row_last = rows.last;
-        k.ablation = p.ablation; k.has_phi = r.has_phi; k.has_zd = r.has_zd;
-        k.q = ad;
-        return mg_lds_adapt(k, st);
-    }
-
-    // CHUNKS: one launch per chunk on the caller's stream; the whole-batch metrics of the chunk on the helper stream, ordered by
-    // the events of lds_schedule.h (per-sample stop: one stream, no metrics, the host ends when every sample has stopped)
-    int lds_run_chunks(LdsRun& r) {
-        LdsArgs& a = r.a;
-        const size_t row = (size_t)MGADMM_NMETRIC * r.Bp;
-        int c = 0;
-        for (; c < r.s.chunks(); ++c) {
-            const ldssched::Chunk ch = r.s.chunk(c);
-            a.first = ch.it0 == 0 && r.cold;      // phi = Ldr x0 is formed by the first iteration of a cold start
-            a.J = ch.Jc;
-            for (int k = 0; k <= ch.Jc; ++k) a.xs[k] = lds_xbuf(r, ch.it0 + k);
-            a.cg_iters = d_cg_iters + (size_t)ch.it0 * 3 * r.Bp;
-            a.it0 = ch.it0;                       // (read with the per-sample stop and with a schedule of weights)
-            if (r.s.per_sample) {
-                a.ps = d_ps_full + (size_t)ch.it0 * row;
-                MG_TRY(launch_lds(a, r.B));
-                MG_TRY(adapt_step(r, ch.it0 + ch.Jc - 1, a.ps + (size_t)(ch.Jc - 1) * row));      // (the sums of every iteration are kept)
-                r.n_done = ch.it0 + ch.Jc;
-                int stopped = 0;
-                MG_TRY(lagged_word(c, a.pstop_count, &stopped));
-                if (stopped == r.B) break;        // the launches enqueued since returned at their guards
-                continue;
-            }
-            a.ps = d_ps_ring + (size_t)ch.set * r.s.J * row;
-            if (ch.wait >= 0) MG_HIP(hipStreamWaitEvent(st, ev_side[ch.wait], 0));
-            MG_TRY(launch_lds(a, r.B));
-            MG_HIP(hipEventRecord(ev_main[ch.ev], st));
-            MG_HIP(hipStreamWaitEvent(st_side, ev_main[ch.ev], 0));
-            // adaptive penalties: the step reads the last row of the chunk's metric set on `st`, in stream order before launch
-            // c + 1; the first launch that writes the set again is launch c + 3 on the same stream, so the hazard rule of
-            // lds_schedule.h holds as it stands (the metric kernels beside it only read the set)
-            MG_TRY(adapt_step(r, ch.it0 + ch.Jc - 1, a.ps + (size_t)(ch.Jc - 1) * row));
-            for (int k = 0; k < ch.Jc; ++k) MG_TRY(lds_batch_metrics(r, ch.it0 + k, a.ps + (size_t)k * row, st_side));
-            MG_HIP(hipEventRecord(ev_side[ch.ev], st_side));
-            r.n_done = ch.it0 + ch.Jc;
-        }
-        if (!r.s.per_sample && r.s.join(c) >= 0) MG_HIP(hipStreamWaitEvent(st, ev_side[r.s.join(c)], 0));
-        return MGADMM_OK;
-    }
-
-    // SYNC and DEVSTOP: one iteration per launch, everything on the caller's stream
-    int lds_run_steps(LdsRun& r) {
-        LdsArgs& a = r.a;
-        const size_t K = p.max_cg_iter;
-        for (int it = 0; it < r.s.max_it; ++it) {
-            a.first = it == 0 && r.cold;          // phi = Ldr x0 is formed by the first launch of a cold start
-            a.J = 1;
-            a.xs[0] = lds_xbuf(r, it); a.xs[1] = lds_xbuf(r, it + 1);
-            a.cg_iters = d_cg_iters + (size_t)it * 3 * r.Bp;
-            a.ps = d_ps;
-            a.it0 = it;                           // (read with the per-sample stop and with a schedule of weights)
-            if (r.s.per_sample) a.ps = d_ps_full + (size_t)it * MGADMM_NMETRIC * r.Bp;
-            if (r.record) {
-                MG_TRY(fill((S*)d_alpha_hist, 3 * K * r.Bp, (S)NAN));
-                MG_TRY(fill((S*)d_beta_hist, 3 * K * r.Bp, (S)NAN));
-            }
-            MG_TRY(launch_lds(a, r.B));
-            MG_TRY(adapt_step(r, it, a.ps));
-            if (!r.s.per_sample) MG_TRY(lds_batch_metrics(r, it, a.ps, st));
-            if (r.record) {
-                for (int w = 0; w < 3; ++w) {
-                    if (w == 2 && !r.has_zd) continue;
-                    double* ao = r.hist->cg_alpha + ((size_t)it * 3 + w) * K * r.B;
-                    double* bo = r.hist->cg_beta + ((size_t)it * 3 + w) * K * r.B;
-                    MG_TRY(fetch_hist(d_alpha_hist + (size_t)w * K * r.Bp, K * r.Bp, ao, r.B, r.Bp, K));
-                    MG_TRY(fetch_hist(d_beta_hist + (size_t)w * K * r.Bp, K * r.Bp, bo, r.B, r.Bp, K));
-                }
-            }
-            r.n_done = it + 1;
-            if (r.s.per_sample) {         // (the host is in step with the device here: the count of this very launch)
-                MG_HIP(hipMemcpyAsync(h_flag + 1, a.pstop_count, sizeof(int), hipMemcpyDeviceToHost, st));
-                MG_HIP(hipStreamSynchronize(st));
-                if (h_flag[1] == r.B) break;
-            } else if (r.s.kind == ldssched::DEVSTOP) {
-                int sw = 0;
-                MG_TRY(mg_lds_stop_test(d_hist + (size_t)it * MGADMM_NMETRIC, d_nonfinite, r.has_phi, r.has_zd, p.admm_tol, it, d_stop, st));
-                MG_TRY(lagged_word(it, d_stop, &sw));
-                if (sw != 0) break;       // the launches enqueued since returned at their guards
-            } else if (p.check_stop) {
-                bool stop = false;
-                MG_TRY(host_stop_test(it, r.has_phi, r.has_zd, &stop, &r.rc));
-                if (stop) break;
-            }
-        }
-        if (r.s.kind == ldssched::DEVSTOP) {
-            // the stop word after everything enqueued has run: 0 = no stop (all enqueued iterations ran), k > 0 = the stop
-            // test passed at the end of iteration k - 1, k < 0 = iteration -k - 1 met a NaN / Inf
-            MG_HIP(hipMemcpyAsync(h_flag + 1, d_stop, sizeof(int), hipMemcpyDeviceToHost, st));
-            MG_HIP(hipStreamSynchronize(st));
-            const int sw = h_flag[1];
-            if (sw > 0) r.n_done = sw;
-            else if (sw < 0) { r.n_done = -sw; r.rc = MGADMM_ERR_NONFINITE; }
-        }
-        return MGADMM_OK;
-    }
-
-    // per-sample stop: r.n_done iterations were enqueued; the history from the stop words and the per-sample sums, the
-    // iterations of every sample to `nps`, the largest of them to r.n_done
-    int lds_finish_per_sample(LdsRun& r, std::vector<int>& nps) {
-        int* const d_nps = d_pstop + Bp_max + 1;
-        MG_TRY(mg_lds_ps_history(d_ps_full, d_pstop, r.n_done, r.s.max_it, r.B, r.Bp, d_nps, d_hist,
-                                 (r.hist && r.hist->metrics_per_sample) ? d_hist_ps : nullptr, st));
-        nps.resize(r.B);
-        MG_HIP(hipMemcpyAsync(nps.data(), d_nps, sizeof(int) * r.B, hipMemcpyDeviceToHost, st));
+    // the CG counts of `rows` iterations: [rows][3][Bp] on the device -> out[rows][3][B]
+    int fetch_cg_iters(int32_t* out, size_t rows, int B, int Bp) {
+        std::vector<int> tmp(rows * 3 * Bp);
+        MG_HIP(hipMemcpyAsync(tmp.data(), d_cg_iters, sizeof(int) * tmp.size(), hipMemcpyDeviceToHost, st));
         MG_HIP(hipStreamSynchronize(st));
-        r.n_done = *std::max_element(nps.begin(), nps.end());
+        for (size_t r = 0; r < rows * 3; ++r) memcpy(out + r * B, tmp.data() + r * Bp, sizeof(int) * B);
         return MGADMM_OK;
     }
-
-    int solve_lds(const void* y, const void* mask, int B, const void* x0, const mgadmm_state* state_in, void* x_out,
-                  const mgadmm_state* state_out, mgadmm_history* hist) {
-        if constexpr (!std::is_same<S, float>::value) {
-            return MGADMM_ERR_UNSUPPORTED;
-        } else {
-            LdsRun r;
-            r.B = B; r.Bp = (B + 63) / 64 * 64;
-            r.has_phi = p.ablation == MGADMM_ABL_NONE || p.ablation == MGADMM_ABL_DGLR;
-            r.has_zd = p.ablation != MGADMM_ABL_DGLR;
-            r.record = p.record_cg_coeffs && hist && hist->cg_alpha && hist->cg_beta;
-            r.cold = !state_in;
-            r.hist = hist;
-            // The caller's output buffers ARE the working state of this path (same (B, T*N) layout): no copy-out at the end
-            // (round 2 until here: seven 120 MB device copies per solve at cfg2 = 0.7 ms of a 59 ms solve).  The iterates are
-            // assigned to buffers so that the one of the LAST iteration lands in x_out (an early stop on another buffer
-            // costs one copy).  Outputs must not alias y / mask (mgadmm.h).
-            r.xo = static_cast<float*>(x_out);
-            r.s = ldssched::Schedule::pick(lds_async != 0, r.record, p.check_stop != 0, p.admm_convergence == MGADMM_ADMM_PER_SAMPLE,
-                                           ad_on ? ldsadapt::adapt_J(ad.every, std::max(1, std::min(lds_chunk, LDS_MAXJ))) : lds_chunk,
-                                           p.max_admm_iter);
-            const ldssched::Schedule& s = r.s;
-            const bool chunked = s.kind == ldssched::CHUNKS;
-            MG_TRY(ensure_hist_ps(hist, B));
-            MG_HIP(hipMemsetAsync(d_nonfinite, 0, sizeof(int), st));
-            MG_HIP(hipMemsetAsync(d_ps, 0, sizeof(double) * MGADMM_NMETRIC * r.Bp, st));
-            MG_HIP(hipMemsetAsync(d_cg_iters, 0, sizeof(int) * (size_t)s.max_it * 3 * r.Bp, st));
-            if (s.per_sample) {
-                MG_TRY(grow(d_ps_full, ps_full_elems, (size_t)s.max_it * MGADMM_NMETRIC * r.Bp));
-                MG_HIP(hipMemsetAsync(d_pstop, 0, sizeof(int) * ((size_t)Bp_max + 1), st));
-            }
-            MG_TRY(lds_ring_reserve(s.slots()));
-            lds_fill_args(r, y, mask);
-            MG_TRY(lds_state_in(r, x0, state_in));
-            if (s.kind == ldssched::DEVSTOP) {
-                r.a.stop = d_stop;
-                MG_HIP(hipMemsetAsync(d_stop, 0, sizeof(int), st));
-            }
-            if (chunked && !s.per_sample) MG_HIP(hipMemsetAsync(d_ps_ring, 0, sizeof(double) * LDS_SETS * s.J * MGADMM_NMETRIC * r.Bp, st));
-            if (s.per_sample) {
-                r.a.pstop = d_pstop; r.a.pstop_count = d_pstop + Bp_max; r.a.x_final = r.xo; r.a.admm_tol = p.admm_tol;
-            }
-            if (sg_B > 0) {                   // (B == sg_B: solve_gate) workgroup b reads the image of set d_sg_set[b]
-                r.a.csr = d_sg_img; r.a.img_stride = ldssets::img_stride(lds); r.a.gset = d_sg_set;
-            }
-            // the table of records the launches read (with one they take the kernels k_admm_lds_pp); trip k of a launch reads
-            // row sched_row(it0 + k, sp_row0, sp_rows) of it
-            const solvegate::TableChoice tc = solvegate::table_of(set_state(), wt.sch_row0, s.max_it);
-            if (tc.scalar_records) MG_TRY(upload_sample_params(B));      // (a graph table without a weights table)
-            switch (tc.table) {
-                case solvegate::TABLE_NONE: break;
-                case solvegate::TABLE_SAMPLE: r.a.sp = d_sp; break;      // (B == sp_B: solve_gate)
-                case solvegate::TABLE_SCHEDULE: MG_TRY(upload_param_schedule(B)); r.a.sp = d_sch; break;
-                case solvegate::TABLE_ADAPTIVE: MG_TRY(adapt_begin(r)); r.a.sp = d_ad_tab; break;      // the steps between the launches write it
-            }
-            r.a.sp_rows = tc.sp_rows; r.a.sp_row0 = tc.sp_row0; r.a.sp_stride = tc.stride_B ? B : 0;
-            MG_TRY(chunked ? lds_run_chunks(r) : lds_run_steps(r));
-            std::vector<int> nps;         // per-sample stop: iterations of every sample
-            if (s.per_sample) MG_TRY(lds_finish_per_sample(r, nps));
-            if (ad_on)      // periods of the history: the start values and the steps that followed an iteration some sample ran
-                ad_last_periods = 1 + (int)std::count_if(r.ad_bounds.begin(), r.ad_bounds.end(), [&](int n) { return n <= r.n_done; });
-            // (per-sample stop: a stopped sample stored x_out[b] itself, the others ran max_it iterations and their last iterate is x_out)
-            float* const xc = s.per_sample ? r.xo : lds_xbuf(r, r.n_done);
-            if (xc != r.xo)       // early stop on another buffer
-                MG_HIP(hipMemcpyAsync(x_out, xc, (size_t)B * T * N * sizeof(float), hipMemcpyDeviceToDevice, st));
-            if (state_out) MG_TRY(lds_state_out(r, state_out));
-            return finish_history(hist, r.n_done, B, r.Bp, r.rc, s.per_sample ? nps.data() : nullptr);
-        }
-    }
-
     // copies the device-side history of a finished solve into the caller's host buffers
     // nps: iterations of every sample of a solve that stopped per sample (its delta_x_per_step is not formed), else nullptr
     int finish_history(mgadmm_history* hist, int n_done, int B, int Bp, int rc_final, const int* nps = nullptr) {
@@ -1955,13 +1404,7 @@ struct Engine : EngineBase {
             if (hist->metrics_per_sample)
                 MG_HIP(hipMemcpyAsync(hist->metrics_per_sample, d_hist_ps, sizeof(double) * (size_t)n_done * MGADMM_NMETRIC * B,
                                       hipMemcpyDeviceToHost, st));
-            if (hist->cg_iters) {
-                std::vector<int> tmp((size_t)n_done * 3 * Bp);
-                MG_HIP(hipMemcpyAsync(tmp.data(), d_cg_iters, sizeof(int) * tmp.size(), hipMemcpyDeviceToHost, st));
-                MG_HIP(hipStreamSynchronize(st));
-                for (size_t r = 0; r < (size_t)n_done * 3; ++r)
-                    memcpy(hist->cg_iters + r * B, tmp.data() + r * Bp, sizeof(int) * B);
-            }
+            if (hist->cg_iters) MG_TRY(fetch_cg_iters(hist->cg_iters, n_done, B, Bp));
         }
         MG_HIP(hipMemcpyAsync(h_flag, d_nonfinite, sizeof(int), hipMemcpyDeviceToHost, st));
         MG_HIP(hipStreamSynchronize(st));
@@ -1974,12 +1417,13 @@ struct Engine : EngineBase {
         return rc_final;
     }
 
-    int save_coeffs(const Geom& q, mgadmm_history* hist, int it, int which, int B) {
+    // the CG coefficients of solve `which` of iteration `it`, which stand at [from][K][Bp] of the device buffers
+    int save_coeffs(int Bp, mgadmm_history* hist, int it, int which, int B, int from = 0) {
         const size_t K = p.max_cg_iter;
         double* a = hist->cg_alpha + ((size_t)it * 3 + which) * K * B;
         double* b = hist->cg_beta + ((size_t)it * 3 + which) * K * B;
-        MG_TRY(fetch_hist(d_alpha_hist, K * q.Bp, a, B, q.Bp, K));
-        return fetch_hist(d_beta_hist, K * q.Bp, b, B, q.Bp, K);
+        MG_TRY(fetch_hist(d_alpha_hist + (size_t)from * K * Bp, K * Bp, a, B, Bp, K));
+        return fetch_hist(d_beta_hist + (size_t)from * K * Bp, K * Bp, b, B, Bp, K);
     }
 };
 

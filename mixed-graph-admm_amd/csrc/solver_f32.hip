@@ -1,4 +1,4 @@
-// float32 engine (streaming kernels + LDS-resident path)
-#include "engine.h"
+// float32 engine (streaming kernels + the driver of the LDS-resident path)
+#include "lds_engine.h"
 
-EngineBase* mg_make_engine_f32(mgadmm_solver* s) { return new Engine<float>(s); }
+EngineBase* mg_make_engine_f32(mgadmm_solver* s) { return new LdsEngine(s); }

@@ -1,4 +1,4 @@
-"""The three schedules of the LDS path's ADMM outer loop (csrc/lds_schedule.h; csrc/engine.h, solve_lds) give the same bits.
+"""The three schedules of the LDS path's ADMM outer loop (csrc/lds_schedule.h; csrc/lds_engine.h, solve_lds) give the same bits.
 
 SYNC (MGADMM_LDS_ASYNC=0): one stream, the host tests the stop criterion (ADMM.py:645-646) after every iteration.
 DEVSTOP (check_stop): the stop test runs on the device, later launches return at their guard, the host looks late.

@@ -1,5 +1,5 @@
 """GPU experiment: wall time of one cfg2 solve (N=307, B=4096, 20 ADMM iterations, LDS path) under the three schedules of the
-outer loop (csrc/engine.h, solve_lds): SYNC (MGADMM_LDS_ASYNC=0), DEVSTOP (check_stop, stop test on the device) and
+outer loop (csrc/lds_engine.h, solve_lds): SYNC (MGADMM_LDS_ASYNC=0), DEVSTOP (check_stop, stop test on the device) and
 OVERLAP (fixed iteration count, metric kernels on the helper stream).  ADMM_tol is set below reach so that all 20 run."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
