@@ -11,10 +11,8 @@ Batched semantics: B samples are B independent reference runs (per-sample CG con
 reference itself cannot run B > 1, ADMM.py:362).  Whole-batch residual norms are the Frobenius norms
 over the batch tensor like ADMM.py:612-636.
 """
-import contextlib
 import ctypes as C
 import itertools
-import math
 
 import numpy as np
 import torch
@@ -22,6 +20,9 @@ import torch
 from . import _lib
 from . import utils as _u
 from .graph import Graph, expand_channels, tables_to_csr
+from .solve_args import (ADAPTIVE_RHO_KEYS, GRAPH_PARAM_NAMES, SAMPLE_PARAM_NAMES, _check_adaptive_rho,  # noqa: F401
+                         _check_graph_sets, _check_param_schedule, _check_sample_params, _float64,
+                         geometric_ramp, parse_solve_args, solve_scope)
 
 __all__ = ["ADMM_algorithm", "initial_guess", "initial_interpolation", "geometric_ramp"]
 
@@ -45,155 +46,33 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-SAMPLE_PARAM_NAMES = ("rho", "rho_u", "rho_d", "mu_u", "mu_d1", "mu_d2")
+class _SolveHistory:
+    """The host arrays ``mgadmm_solve`` writes its history to and ``c``, the ``_lib.History`` that points to them.  ``dxps`` is
+    None with per-sample stopping, ``mps`` without ``per_sample``, ``al`` and ``be`` unless the CG coefficients are recorded."""
 
+    def __init__(self, p, B, T, per_sample):
+        K, I = p.max_cg_iter, p.max_admm_iter
+        f64, i32 = (lambda a: a.ctypes.data_as(C.POINTER(C.c_double))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)))
+        self.c = hs = _lib.History()
+        self.metrics = np.zeros((I, _lib.NMETRIC), dtype=np.float64)
+        self.cg_it = np.zeros((I, 3, B), dtype=np.int32)
+        self.nps = np.zeros(B, dtype=np.int32)
+        hs.metrics, hs.cg_iters, hs.n_iters_per_sample = f64(self.metrics), i32(self.cg_it), i32(self.nps)
+        self.dxps = self.mps = self.al = self.be = None
+        if p.admm_convergence != _lib.ADMM_PER_SAMPLE:          # not formed when samples stop on their own (include/mgadmm.h)
+            self.dxps = np.zeros((I, T), dtype=np.float64)
+            hs.delta_x_per_step = f64(self.dxps)
+        if per_sample:
+            self.mps = np.zeros((I, _lib.NMETRIC, B), dtype=np.float64)
+            hs.metrics_per_sample = f64(self.mps)
+        if p.record_cg_coeffs:
+            self.al, self.be = (np.full((I, 3, K, B), np.nan, dtype=np.float64) for _ in range(2))
+            hs.cg_alpha, hs.cg_beta = f64(self.al), f64(self.be)
 
-def _check_sample_params(sample_params, B):
-    """``sample_params`` of ``solve``: dict name -> 1-D sequence / tensor of length B, as a dict name -> float64 array.
-    Raises ValueError for an unknown name, a wrong length, a value that is not finite, rho* <= 0 or mu* < 0 (what
-    ``mgadmm_solver_set_sample_params`` refuses, found before the library is touched)."""
-    if not hasattr(sample_params, "items"):
-        raise ValueError(f"sample_params must be a dict with keys out of {SAMPLE_PARAM_NAMES}, got {type(sample_params).__name__}")
-    out = {}
-    for name, vals in sample_params.items():
-        if name not in SAMPLE_PARAM_NAMES:
-            raise ValueError(f"sample_params: unknown key {name!r} (expected some of {SAMPLE_PARAM_NAMES})")
-        v = vals.detach().cpu().numpy() if torch.is_tensor(vals) else np.asarray(vals)
-        v = np.ascontiguousarray(v, dtype=np.float64)
-        if v.ndim != 1 or v.shape[0] != B:
-            raise ValueError(f"sample_params[{name!r}] must be 1-D of length B = {B}, got shape {tuple(v.shape)}")
-        if not np.isfinite(v).all():
-            raise ValueError(f"sample_params[{name!r}][{int(np.nonzero(~np.isfinite(v))[0][0])}] is not finite")
-        bad = np.nonzero(v <= 0 if name.startswith("rho") else v < 0)[0]
-        if bad.size:
-            raise ValueError(f"sample_params[{name!r}][{int(bad[0])}] = {v[bad[0]]}: "
-                             + ("rho, rho_u and rho_d must be > 0" if name.startswith("rho") else "mu_u, mu_d1 and mu_d2 must be >= 0"))
-        out[name] = v
-    return out
-
-
-ADAPTIVE_RHO_KEYS = ("every", "mu", "tau", "until", "rho_min", "rho_max")
-
-
-def _check_adaptive_rho(adaptive_rho, adaptive_start=0):
-    """``adaptive_rho`` of ``solve``: dict with ``every`` (1 ... 16), ``mu`` > 1 (default 10), ``tau`` > 1 (default 2), ``until``
-    (None: no limit), ``rho_min`` / ``rho_max`` (a number for all three penalties, or three in the order rho, rho_u, rho_d, or a
-    dict by name; defaults 1e-6 / 1e6) -> the ``_lib.AdaptiveRho`` struct.  ValueError for what
-    ``mgadmm_solver_set_adaptive_rho`` refuses, found before the library is touched."""
-    if not hasattr(adaptive_rho, "items"):
-        raise ValueError(f"adaptive_rho must be a dict with keys out of {ADAPTIVE_RHO_KEYS}, got {type(adaptive_rho).__name__}")
-    for k2 in adaptive_rho:
-        if k2 not in ADAPTIVE_RHO_KEYS:
-            raise ValueError(f"adaptive_rho: unknown key {k2!r} (expected some of {ADAPTIVE_RHO_KEYS})")
-    if adaptive_rho.get("every") is None:
-        raise ValueError("adaptive_rho needs 'every' (iterations between two adaptation steps, 1 ... 16)")
-    every, start = int(adaptive_rho["every"]), int(adaptive_start)
-    until = adaptive_rho.get("until")
-    until = 0 if until is None else int(until)
-    mu, tau = float(adaptive_rho.get("mu", 10.0)), float(adaptive_rho.get("tau", 2.0))
-    if not 1 <= every <= 16:
-        raise ValueError(f"adaptive_rho: every = {every} outside [1, 16] (the iterations of one launch)")
-    if not mu > 1.0 or not tau > 1.0:
-        raise ValueError(f"adaptive_rho: mu = {mu} and tau = {tau} should both be > 1")
-    if until < 0:
-        raise ValueError(f"adaptive_rho: until = {until} is negative (None: no limit)")
-    if start < 0 or start % every:
-        raise ValueError(f"adaptive_start = {start} must be a non-negative multiple of every = {every}")
-
-    def three(name, default):
-        v = adaptive_rho.get(name)
-        if v is None:
-            return [default] * 3
-        if hasattr(v, "items"):
-            if set(v) - set(SAMPLE_PARAM_NAMES[:3]):
-                raise ValueError(f"adaptive_rho[{name!r}]: unknown keys {sorted(set(v) - set(SAMPLE_PARAM_NAMES[:3]))}")
-            return [float(v.get(nm, default)) for nm in SAMPLE_PARAM_NAMES[:3]]
-        a = np.asarray(v, dtype=np.float64)
-        if a.ndim == 0:
-            return [float(a)] * 3
-        if a.shape != (3,):
-            raise ValueError(f"adaptive_rho[{name!r}] must be a number, three numbers (rho, rho_u, rho_d) or a dict by name")
-        return [float(t) for t in a]
-    lo, hi = three("rho_min", 1e-6), three("rho_max", 1e6)
-    for nm, a, b in zip(SAMPLE_PARAM_NAMES[:3], lo, hi):
-        if not (0.0 < a <= b < float("inf")):
-            raise ValueError(f"adaptive_rho: rho_min[{nm}] = {a}, rho_max[{nm}] = {b}, should be 0 < rho_min <= rho_max (finite)")
-    ar = _lib.AdaptiveRho(every=every, until=until, mu=mu, tau=tau)
-    ar.rho_min[:], ar.rho_max[:] = lo, hi
-    return ar, start
-
-
-def _check_param_schedule(param_schedule, B, schedule_start=0, sample_params=None):
-    """``param_schedule`` of ``solve``: dict name -> array of shape (K,) (shared form) or (K, B) (per-sample form), the same K
-    and the same form for every name, as ``(dict name -> float64 array, K, 0 or B)``.  Raises ValueError for an unknown name,
-    a wrong shape, a value that is not finite, rho* <= 0 or mu* < 0 (named by [row][b]), a name that ``sample_params`` gives
-    too, or a negative ``schedule_start`` (what ``mgadmm_solver_set_param_schedule`` refuses, found before the library is
-    touched)."""
-    if not hasattr(param_schedule, "items"):
-        raise ValueError(f"param_schedule must be a dict with keys out of {SAMPLE_PARAM_NAMES}, got {type(param_schedule).__name__}")
-    if int(schedule_start) != schedule_start or schedule_start < 0:
-        raise ValueError(f"schedule_start must be an integer >= 0, got {schedule_start!r}")
-    out, shape = {}, None
-    for name, vals in param_schedule.items():
-        if name not in SAMPLE_PARAM_NAMES:
-            raise ValueError(f"param_schedule: unknown key {name!r} (expected some of {SAMPLE_PARAM_NAMES})")
-        if sample_params is not None and name in sample_params:
-            raise ValueError(f"param_schedule[{name!r}] is given twice: in param_schedule and in sample_params")
-        v = vals.detach().cpu().numpy() if torch.is_tensor(vals) else np.asarray(vals)
-        v = np.ascontiguousarray(v, dtype=np.float64) if v.ndim else v          # (ascontiguousarray turns a scalar into (1,))
-        if v.ndim not in (1, 2) or v.shape[0] < 1 or (v.ndim == 2 and v.shape[1] != B):
-            raise ValueError(f"param_schedule[{name!r}] must have shape (K,) or (K, B = {B}) with K >= 1, got shape {tuple(v.shape)}")
-        if shape is not None and v.shape != shape:
-            raise ValueError(f"param_schedule[{name!r}] has shape {tuple(v.shape)}, the entries before it {tuple(shape)}: "
-                             "one number of rows and one form (shared or per-sample) for all")
-        shape = v.shape
-        at = lambda idx: "".join(f"[{int(i)}]" for i in idx)
-        if not np.isfinite(v).all():
-            raise ValueError(f"param_schedule[{name!r}]{at(np.argwhere(~np.isfinite(v))[0])} is not finite")
-        bad = np.argwhere(v <= 0 if name.startswith("rho") else v < 0)
-        if bad.size:
-            raise ValueError(f"param_schedule[{name!r}]{at(bad[0])} = {v[tuple(bad[0])]}: "
-                             + ("rho, rho_u and rho_d must be > 0" if name.startswith("rho") else "mu_u, mu_d1 and mu_d2 must be >= 0"))
-        out[name] = v
-    if shape is None:
-        return out, 0, 0
-    return out, int(shape[0]), (int(shape[1]) if len(shape) == 2 else 0)
-
-
-def geometric_ramp(v0, factor, n_rows, vmax=None):
-    """Rows of a geometric schedule: ``v0 * factor ** row`` for row = 0 .. n_rows - 1 as a float64 array, capped at ``vmax``
-    when given (``solve(param_schedule={'rho': geometric_ramp(rho, 1.1, 20)})``; the last row holds for the rest of a solve)."""
-    if int(n_rows) != n_rows or n_rows < 1:
-        raise ValueError(f"geometric_ramp: n_rows must be an integer >= 1, got {n_rows!r}")
-    if not (np.isfinite(v0) and np.isfinite(factor) and v0 > 0 and factor > 0):
-        raise ValueError(f"geometric_ramp: v0 and factor must be finite and > 0, got {v0!r}, {factor!r}")
-    v = float(v0) * float(factor) ** np.arange(int(n_rows), dtype=np.float64)
-    return v if vmax is None else np.minimum(v, float(vmax))
-
-
-GRAPH_PARAM_NAMES = ("u_sigma", "d_sigma")
-
-
-def _check_graph_params(graph_params, B):
-    """``graph_params`` of ``solve``: dict with u_sigma and / or d_sigma -> 1-D sequence / tensor of length B, as a dict
-    name -> float64 array.  Raises ValueError for an unknown name, a wrong length, a value that is not finite or <= 0."""
-    if not hasattr(graph_params, "items"):
-        raise ValueError(f"graph_params must be a dict with keys out of {GRAPH_PARAM_NAMES}, got {type(graph_params).__name__}")
-    out = {}
-    for name, vals in graph_params.items():
-        if name not in GRAPH_PARAM_NAMES:
-            raise ValueError(f"graph_params: unknown key {name!r} (expected some of {GRAPH_PARAM_NAMES})")
-        v = vals.detach().cpu().numpy() if torch.is_tensor(vals) else np.asarray(vals)
-        v = np.ascontiguousarray(v, dtype=np.float64)
-        if v.ndim != 1 or v.shape[0] != B:
-            raise ValueError(f"graph_params[{name!r}] must be 1-D of length B = {B}, got shape {tuple(v.shape)}")
-        if not np.isfinite(v).all():
-            raise ValueError(f"graph_params[{name!r}][{int(np.nonzero(~np.isfinite(v))[0][0])}] is not finite")
-        bad = np.nonzero(v <= 0)[0]
-        if bad.size:
-            raise ValueError(f"graph_params[{name!r}][{int(bad[0])}] = {v[bad[0]]}: u_sigma and d_sigma must be > 0")
-        out[name] = v
-    return out
+    def ran(self):
+        """The arguments of ``_fill_history`` for the iterations that ran."""
+        n = self.c.n_iters
+        return self.metrics[:n], (None if self.dxps is None else self.dxps[:n]), self.cg_it[:n], self.al, self.be
 
 
 class ADMM_algorithm():
@@ -451,116 +330,7 @@ class ADMM_algorithm():
         self._solvers[(Cn, dtype)] = [h, int(B)]
         return h, p
 
-    @contextlib.contextmanager
-    def _sample_table(self, h, sp, B):
-        """Per-sample ADMM weights (``_check_sample_params`` output) set on solver ``h`` for the solves inside the block and
-        cleared after it: the next solve of the instance is an ordinary one."""
-        if not sp:
-            yield
-            return
-        spc = _lib.SampleParams()
-        for nm, v in sp.items():
-            setattr(spc, nm, v.ctypes.data_as(C.POINTER(C.c_double)))
-        _lib.check(_lib.lib.mgadmm_solver_set_sample_params(h, C.byref(spc), B))
-        try:
-            yield
-        finally:
-            _lib.lib.mgadmm_solver_set_sample_params(h, None, 0)
-
-    @contextlib.contextmanager
-    def _schedule_table(self, h, sch, first_row):
-        """Per-iteration ADMM weights (``_check_param_schedule`` output) set on solver ``h`` for the solves inside the block and
-        cleared after it, like ``_sample_table``."""
-        if sch is None or not sch[0]:
-            yield
-            return
-        arrays, n_rows, cols = sch
-        sc = _lib.ParamSchedule()
-        for nm, v in arrays.items():
-            setattr(sc, nm, v.ctypes.data_as(C.POINTER(C.c_double)))
-        _lib.check(_lib.lib.mgadmm_solver_set_param_schedule(h, C.byref(sc), n_rows, cols, int(first_row)))
-        try:
-            yield
-        finally:
-            _lib.lib.mgadmm_solver_set_param_schedule(h, None, 0, 0, 0)
-
-    @contextlib.contextmanager
-    def _adaptive(self, h, ar):
-        """Adaptive penalties (``_check_adaptive_rho`` output) set on solver ``h`` for the solves inside the block and cleared
-        after it, like ``_sample_table``."""
-        if ar is None:
-            yield
-            return
-        _lib.check(_lib.lib.mgadmm_solver_set_adaptive_rho(h, C.byref(ar[0]), ar[1]))
-        try:
-            yield
-        finally:
-            _lib.lib.mgadmm_solver_set_adaptive_rho(h, None, 0)
-
-    def _check_graph_sets(self, graph_sets, graph_of_sample, graph_params, B):
-        """The graph arguments of ``solve`` as ``(sets, set_of_sample)`` -- a list of (u_ew, d_ew) tables and an int32 array of
-        length B -- or None without them.  ValueError for what can be refused before the library is touched."""
-        if graph_params is None and graph_sets is None:
-            if graph_of_sample is not None:
-                raise ValueError("graph_of_sample needs graph_sets")
-            return None
-        if graph_params is not None and graph_sets is not None:
-            raise ValueError("graph_params and graph_sets exclude each other (graph_params builds the sets itself)")
-        if self.use_line_graph:
-            raise ValueError("graph_params / graph_sets: a line-graph instance has no spatial W_d tables to vary (use_line_graph=True)")
-        if graph_params is not None:
-            gp = _check_graph_params(graph_params, B)
-            if getattr(self, "dist_list", None) is None:
-                raise ValueError("graph_params: the instance was built without distances (dist_list), its tables cannot be rebuilt")
-            cols = [gp[nm].tolist() if nm in gp else [getattr(self, nm)] * B for nm in GRAPH_PARAM_NAMES]
-            pairs, index = [], {}
-            gos = np.zeros(B, dtype=np.int32)
-            for b, pair in enumerate(zip(*cols)):
-                if pair not in index:
-                    index[pair] = len(pairs)
-                    pairs.append(pair)
-                gos[b] = index[pair]
-            return [self._weight_tables(us, ds)[:2] for us, ds in pairs], gos
-        sets = []
-        for j, pair in enumerate(graph_sets):
-            if not isinstance(pair, (tuple, list)) or len(pair) != 2:
-                raise ValueError(f"graph_sets[{j}] must be a pair (u_ew, d_ew)")
-            u_ew, d_ew = (torch.as_tensor(t).float() for t in pair)
-            for nm, t, own in (("u_ew", u_ew, self.u_ew), ("d_ew", d_ew, self.d_ew)):
-                if tuple(t.shape) not in (tuple(own.shape), tuple(own.shape[-2:])):
-                    raise ValueError(f"graph_sets[{j}]: {nm} has shape {tuple(t.shape)}, the instance's has {tuple(own.shape)}")
-            sets.append((u_ew, d_ew))
-        if not sets:
-            raise ValueError("graph_sets is empty")
-        if graph_of_sample is None:
-            raise ValueError("graph_sets needs graph_of_sample (the set of every sample)")
-        gos = graph_of_sample.detach().cpu().numpy() if torch.is_tensor(graph_of_sample) else np.asarray(graph_of_sample)
-        if gos.ndim != 1 or gos.shape[0] != B or gos.dtype.kind not in "iu":
-            raise ValueError(f"graph_of_sample must be B = {B} integers, got shape {tuple(gos.shape)} of {gos.dtype}")
-        bad = np.nonzero((gos < 0) | (gos >= len(sets)))[0]
-        if bad.size:
-            raise ValueError(f"graph_of_sample[{int(bad[0])}] = {int(gos[bad[0]])} out of range for {len(sets)} graph sets")
-        return sets, np.ascontiguousarray(gos, dtype=np.int32)
-
-    @contextlib.contextmanager
-    def _graph_table(self, h, Cn, gs, B):
-        """Per-sample graph weights (``_check_graph_sets`` output) set on solver ``h`` for the solves inside the block: a device
-        graph per set, closed when the block ends, where the table is cleared as well."""
-        if gs is None:
-            yield
-            return
-        sets, gos = gs
-        graphs = []
-        try:
-            for u_ew, d_ew in sets:
-                graphs.append(self._make_graph(Cn, u_ew, d_ew))
-            handles = (C.c_void_p * len(graphs))(*[g.handle for g in graphs])
-            _lib.check(_lib.lib.mgadmm_solver_set_sample_graphs(h, len(graphs), handles, gos.ctypes.data_as(C.POINTER(C.c_int32)), B))
-            yield
-        finally:
-            _lib.lib.mgadmm_solver_set_sample_graphs(h, 0, None, None, 0)
-            for g in graphs:
-                g.close()
+    _check_graph_sets = _check_graph_sets
 
     def _dtype_for(self, t):
         if self.compute_dtype == 'match':
@@ -577,6 +347,43 @@ class ADMM_algorithm():
         if time_steps is not None and t.shape[1] != time_steps:
             raise ValueError(f"{name} has {t.shape[1]} time steps, expected {time_steps}")
         return t.to(device=self.device, dtype=dtype).contiguous()
+
+    def _stage_input(self, y, mask, differential):
+        """``y`` and ``mask`` of ``solve`` / ``two_loops`` on the device: ``(dtype, y, mask or None, mask_f32, (B, N, C))``."""
+        if differential:
+            assert mask is None, 'differential mode does not support mask'   # flag has no other effect (Q3)
+        dt = self._dtype_for(y)
+        yd = self._dev_tensor(y, dt, "y", self.t_in if mask is None else self.T)
+        B, _, N, Cn = yd.shape
+        md, mask_f32 = None, 0
+        if mask is not None:
+            if tuple(mask.shape) != tuple(y.shape):
+                raise ValueError(f"mask shape {tuple(mask.shape)} != y shape {tuple(y.shape)}")
+            mask_f32 = int(mask.dtype == torch.float32)
+            md = self._dev_tensor(mask, dt, "mask", self.T)
+        return dt, yd, md, mask_f32, (B, N, Cn)
+
+    def _has(self):
+        """``(has_phi, has_zd)``: the iterates the ablation keeps."""
+        return self.ablation in ('None', 'DGLR'), self.ablation != 'DGLR'
+
+    def _out_state(self, x, wanted=True):
+        """``(_lib.State, dict name -> tensor like x)`` for the final iterates the ablation has; both empty unless ``wanted``."""
+        names = ("zu", "zd", "gamma_u", "gamma_d") + (("phi", "gamma") if self._has()[0] else ())
+        state = {nm: torch.empty_like(x) for nm in names if wanted}
+        return _lib.State(**{nm: t.data_ptr() for nm, t in state.items()}), state
+
+    def _warm_state(self, warm_start, dt, x):
+        """``warm_start`` of ``solve`` on the device as ``(x, _lib.State, the tensors)``; ValueError for a missing key or shape."""
+        has_phi, has_zd = self._has()
+        need = ["x", "zu", "gamma_u"] + (["zd", "gamma_d"] if has_zd else []) + (["phi", "gamma"] if has_phi else [])
+        missing = [k2 for k2 in need if warm_start.get(k2) is None]
+        if missing:
+            raise ValueError(f"warm_start misses {missing} (ablation {self.ablation!r})")
+        win = {k2: self._dev_tensor(warm_start[k2], dt, "warm_start." + k2, self.T) for k2 in need}
+        if any(tuple(v.shape) != tuple(x.shape) for v in win.values()):
+            raise ValueError("warm_start tensors must have the shape of x (B, T, N, C)")
+        return win["x"], _lib.State(**{nm: win[nm].data_ptr() for nm in need[1:]}), win
 
     def _run_tensor_op(self, fn_name, x, *extra, pre=()):
         """Common driver of the tensor -> tensor entry points: (B,T,N,C) in, same shape/dtype/device out."""
@@ -680,26 +487,11 @@ class ADMM_algorithm():
         ``max_inner_iter`` inner (x, zu, zd, gamma_u, gamma_d) updates restarted in every outer iteration.  Like the
         reference it returns None and appends the CG counts of every inner iteration to ``CG_iter_x/zu/zd``; the final
         iterate is kept in ``self.state`` (x, zu, zd, phi, gamma, gamma_u, gamma_d)."""
-        if differential:
-            assert mask is None, 'differential mode does not support mask'
-        dt = self._dtype_for(y)
-        yd = self._dev_tensor(y, dt, "y", self.t_in if mask is None else self.T)
-        B, _, N, Cn = yd.shape
-        md, mask_f32 = None, 0
-        if mask is not None:
-            if tuple(mask.shape) != tuple(y.shape):
-                raise ValueError(f"mask shape {tuple(mask.shape)} != y shape {tuple(y.shape)}")
-            mask_f32 = int(mask.dtype == torch.float32)
-            md = self._dev_tensor(mask, dt, "mask", self.T)
+        dt, yd, md, mask_f32, (B, N, Cn) = self._stage_input(y, mask, differential)
         h, p = self._solver(Cn, dt, B)
         x = torch.empty((B, self.T, N, Cn), device=yd.device, dtype=dt)
-        has_phi, has_zd = self.ablation in ('None', 'DGLR'), self.ablation != 'DGLR'
-        st, state = _lib.State(), {}
-        for nm in ("zu", "zd", "phi", "gamma", "gamma_u", "gamma_d"):
-            if nm in ("phi", "gamma") and not has_phi:
-                continue
-            state[nm] = torch.empty_like(x)
-            setattr(st, nm, state[nm].data_ptr())
+        has_zd = self._has()[1]
+        st, state = self._out_state(x)
         rows = p.max_admm_iter * p.max_inner_iter
         cg_it = np.zeros((rows, 3, B), dtype=np.int32)
         hs = _lib.History()
@@ -758,106 +550,42 @@ class ADMM_algorithm():
         values of every sample.  A resumed solve passes ``rho_final`` as ``sample_params`` and ``adaptive_start`` = the
         iterations done (a multiple of ``every``).  LDS-resident float32 path only; not together with ``param_schedule``;
         with ``check_stop`` it needs ``admm_convergence='per_sample'``.  For this call only."""
-        sp = _check_sample_params(sample_params, y.shape[0]) if sample_params is not None else None
-        sch = (_check_param_schedule(param_schedule, y.shape[0], schedule_start, sp) if param_schedule is not None else None)
-        gs = self._check_graph_sets(graph_sets, graph_of_sample, graph_params, y.shape[0])
-        ar = _check_adaptive_rho(adaptive_rho, adaptive_start) if adaptive_rho is not None else None
-        if ar is not None and sch is not None:
-            raise ValueError("adaptive_rho and param_schedule exclude each other (the adaptation writes the table a schedule would fill)")
+        args = parse_solve_args(self, y.shape[0], sample_params, graph_sets, graph_of_sample, graph_params, param_schedule,
+                                schedule_start, adaptive_rho, adaptive_start)
         self.rho_history = self.rho_final = None
-        if differential:
-            assert mask is None, 'differential mode does not support mask'   # flag has no other effect (Q3)
-        dt = self._dtype_for(y)
-        ts_y = self.t_in if mask is None else self.T
-        yd = self._dev_tensor(y, dt, "y", ts_y)
-        B, _, N, Cn = yd.shape
-        md = None
-        mask_f32 = 0
-        if mask is not None:
-            if tuple(mask.shape) != tuple(y.shape):
-                raise ValueError(f"mask shape {tuple(mask.shape)} != y shape {tuple(y.shape)}")
-            mask_f32 = int(mask.dtype == torch.float32)
-            md = self._dev_tensor(mask, dt, "mask", self.T)
+        dt, yd, md, mask_f32, (B, N, Cn) = self._stage_input(y, mask, differential)
         h, p = self._solver(Cn, dt, B)
-        dev = yd.device
-        x = torch.empty((B, self.T, N, Cn), device=dev, dtype=dt)
-        has_phi = self.ablation in ('None', 'DGLR')
-        has_zd = self.ablation != 'DGLR'
-        st = _lib.State()
-        state = {}
-        if return_state:
-            for nm in ("zu", "zd", "phi", "gamma", "gamma_u", "gamma_d"):
-                if (nm in ("phi", "gamma") and not has_phi):
-                    continue
-                state[nm] = torch.empty_like(x)
-                setattr(st, nm, state[nm].data_ptr())
-        K, I = p.max_cg_iter, p.max_admm_iter
-        metrics = np.zeros((I, _lib.NMETRIC), dtype=np.float64)
-        dxps = np.zeros((I, self.T), dtype=np.float64)
-        cg_it = np.zeros((I, 3, B), dtype=np.int32)
-        hs = _lib.History()
-        hs.metrics = metrics.ctypes.data_as(C.POINTER(C.c_double))
-        hs.delta_x_per_step = dxps.ctypes.data_as(C.POINTER(C.c_double))
-        hs.cg_iters = cg_it.ctypes.data_as(C.POINTER(C.c_int32))
-        nps = np.zeros(B, dtype=np.int32)
-        hs.n_iters_per_sample = nps.ctypes.data_as(C.POINTER(C.c_int32))
-        if p.admm_convergence == _lib.ADMM_PER_SAMPLE:
-            dxps = None               # not formed when samples stop on their own (include/mgadmm.h)
-            hs.delta_x_per_step = None
-        mps = None
-        if per_sample_history:
-            mps = np.zeros((I, _lib.NMETRIC, B), dtype=np.float64)
-            hs.metrics_per_sample = mps.ctypes.data_as(C.POINTER(C.c_double))
-        al = be = None
-        if p.record_cg_coeffs:
-            al = np.full((I, 3, K, B), np.nan, dtype=np.float64)
-            be = np.full((I, 3, K, B), np.nan, dtype=np.float64)
-            hs.cg_alpha = al.ctypes.data_as(C.POINTER(C.c_double))
-            hs.cg_beta = be.ctypes.data_as(C.POINTER(C.c_double))
-        with self._sample_table(h, sp, B), self._graph_table(h, Cn, gs, B), self._schedule_table(h, sch, schedule_start), \
-                self._adaptive(h, ar):
+        x = torch.empty((B, self.T, N, Cn), device=yd.device, dtype=dt)
+        st, state = self._out_state(x, return_state)
+        hist = _SolveHistory(p, B, self.T, per_sample_history)
+        with solve_scope(self, h, Cn, B, args):
             if warm_start is None:
-                rc = _lib.lib.mgadmm_solve(h, _ptr(yd), _ptr(md), mask_f32, B, _ptr(x), C.byref(st), C.byref(hs),
-                                           _stream_ptr(dev))
+                rc = _lib.lib.mgadmm_solve(h, _ptr(yd), _ptr(md), mask_f32, B, _ptr(x), C.byref(st), C.byref(hist.c),
+                                           _stream_ptr(yd.device))
             else:
-                need = ["x", "zu", "gamma_u"] + (["zd", "gamma_d"] if has_zd else []) + (["phi", "gamma"] if has_phi else [])
-                missing = [k2 for k2 in need if warm_start.get(k2) is None]
-                if missing:
-                    raise ValueError(f"warm_start misses {missing} (ablation {self.ablation!r})")
-                win = {k2: self._dev_tensor(warm_start[k2], dt, "warm_start." + k2, self.T) for k2 in need}
-                if any(tuple(v.shape) != tuple(x.shape) for v in win.values()):
-                    raise ValueError("warm_start tensors must have the shape of x (B, T, N, C)")
-                sin = _lib.State()
-                for nm in need[1:]:
-                    setattr(sin, nm, win[nm].data_ptr())
-                rc = _lib.lib.mgadmm_solve_from(h, _ptr(yd), _ptr(md), mask_f32, B, _ptr(win["x"]), C.byref(sin), _ptr(x),
-                                                C.byref(st), C.byref(hs), _stream_ptr(dev))
-        n = hs.n_iters
-        self.n_iters_per_sample = nps
-        if ar is not None and rc in (_lib.OK, _lib.ERR_NONFINITE):
+                x0, sin, _keep = self._warm_state(warm_start, dt, x)
+                rc = _lib.lib.mgadmm_solve_from(h, _ptr(yd), _ptr(md), mask_f32, B, _ptr(x0), C.byref(sin), _ptr(x),
+                                                C.byref(st), C.byref(hist.c), _stream_ptr(yd.device))
+        n = hist.c.n_iters
+        self.n_iters_per_sample = hist.nps
+        if args.ar is not None and rc in (_lib.OK, _lib.ERR_NONFINITE):
             self._fetch_rho_history(h, B)
-        if dxps is not None:
-            dxps = dxps[:n]
+        if rc != _lib.ERR_NONFINITE:
+            _lib.check(rc)
+        # like the reference at its asserts (ADMM.py:534-606), the history of the iterations that ran is available after ERR_NONFINITE
+        self._fill_history(*hist.ran(), B, *self._has(), print_info and rc == _lib.OK)
+        if hist.mps is not None:
+            self.metrics_per_sample = hist.mps[:n]
         if rc == _lib.ERR_NONFINITE:
-            # like the reference at its asserts (ADMM.py:534-606), the history of the iterations that ran is available
-            self._fill_history(metrics[:n], dxps, cg_it[:n], al, be, B, has_phi, has_zd, False)
             bad = ""
-            if mps is not None:
-                self.metrics_per_sample = mps[:n]
-                idx = np.nonzero(~np.isfinite(mps[:n]).all(axis=(0, 1)))[0]
-                self.nonfinite_samples = idx
+            if hist.mps is not None:
+                idx = self.nonfinite_samples = np.nonzero(~np.isfinite(hist.mps[:n]).all(axis=(0, 1)))[0]
                 bad = f"; non-finite samples: {idx[:16].tolist()}{' ...' if idx.size > 16 else ''}"
             raise AssertionError("NaN/Inf value in the ADMM iterates (reference asserts, ADMM.py:534-606): "
                                  + _lib.lib.mgadmm_last_error().decode() + bad)
-        _lib.check(rc)
-        self._fill_history(metrics[:n], dxps, cg_it[:n], al, be, B, has_phi, has_zd, print_info)
-        if mps is not None:
-            self.metrics_per_sample = mps[:n]
         back = lambda t: t.to(device=y.device, dtype=y.dtype)
         xo = back(x)
-        zu = back(state["zu"]) if "zu" in state else None
-        zd = back(state["zd"]) if "zd" in state else None
-        phi = back(state["phi"]) if "phi" in state else None
+        zu, zd, phi = (back(state[nm]) if nm in state else None for nm in ("zu", "zd", "phi"))
         self.state = {k2: back(v) for k2, v in state.items()}
         self.state["x"] = xo
         return xo, (zu, zd), phi, self.history()
@@ -881,12 +609,8 @@ class ADMM_algorithm():
         """``y`` (B, t_in, N, C) [or (B, T, N, C) with ``mask``] -> ``x`` (B, T, N, C), dtype/device of y.
         History attributes are filled like the reference's (ADMM.py:612-643).  ``sample_params``, ``param_schedule`` and the
         graph arguments (``graph_params``, ``graph_sets``, ``graph_of_sample``) and ``adaptive_rho``: see ``solve``."""
-        if param_schedule is not None:
-            graph_kw = dict(graph_kw, param_schedule=param_schedule)
-        if adaptive_rho is not None:
-            graph_kw = dict(graph_kw, adaptive_rho=adaptive_rho)
         return self.solve(y, mask=mask, differential=differential, print_info=print_info, return_state=False,
-                          sample_params=sample_params, **graph_kw)[0]
+                          sample_params=sample_params, param_schedule=param_schedule, adaptive_rho=adaptive_rho, **graph_kw)[0]
 
     def sweep(self, y, grid, mask=None, chunk=None, schedules=None, **solve_kw):
         """A grid search over ADMM weights and graph sigmas as one batch (the reference's notebooks run one ``combined_loop``
@@ -909,8 +633,7 @@ class ADMM_algorithm():
                 raise ValueError(f"sweep: unknown schedule key {nm!r} (expected some of {SAMPLE_PARAM_NAMES})")
             if nm in grid:
                 raise ValueError(f"sweep: {nm!r} is given twice: in grid and in schedules")
-        cands = {nm: [np.asarray(c.detach().cpu().numpy() if torch.is_tensor(c) else c, dtype=np.float64) for c in schedules[nm]]
-                 for nm in sched_names}
+        cands = {nm: [_float64(c) for c in schedules[nm]] for nm in sched_names}
         if sched_names:
             shapes = {c.shape for cs in cands.values() for c in cs}
             if len(shapes) != 1 or len(next(iter(shapes))) != 1 or next(iter(shapes))[0] < 1:

@@ -15,6 +15,14 @@ def rel(a, b):
     return d / n if n > 0 else d
 
 
+def _tiny(**kw):
+    """The two-node instance of the CPU checks of solve()'s arguments."""
+    from mgadmm.ADMM import ADMM_algorithm
+    cl = torch.tensor([[0, 1], [1, 0]])
+    return ADMM_algorithm({"n_nodes": 2}, dict(rho=1, rho_u=1, rho_d=1, mu_u=1, mu_d1=1, mu_d2=1), use_kNN=True,
+                          u_sigma=1.0, d_sigma=1.0, tables=(cl, torch.tensor([[0.0, 1.0], [0.0, 1.0]])), **kw)
+
+
 def make_oracle(meta, mode, ablation="None", bug_compat=True, prefix="knn", T=None, t_in=None):
     info = admm_info_from(meta)
     T = int(meta["T"]) if T is None else T

@@ -28,7 +28,7 @@ from conftest import PKG, ROOT
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import adaptive_rho_cases as ac               # noqa: E402
-from helpers import rel                       # noqa: E402
+from helpers import _tiny, rel                # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -149,13 +149,6 @@ def test_header_binding_and_symbols_agree():
 
 
 # ------------------------------------------------------------------------------------------------ Python validation
-def _tiny(**kw):
-    from mgadmm.ADMM import ADMM_algorithm
-    cl = torch.tensor([[0, 1], [1, 0]])
-    return ADMM_algorithm({"n_nodes": 2}, dict(rho=1, rho_u=1, rho_d=1, mu_u=1, mu_d1=1, mu_d2=1), use_kNN=True,
-                          u_sigma=1.0, d_sigma=1.0, tables=(cl, torch.tensor([[0.0, 1.0], [0.0, 1.0]])), **kw)
-
-
 BAD = [
     (dict(adaptive_rho=[4, 10, 2]), "must be a dict"),
     (dict(adaptive_rho={"every": 4, "nu": 2}), "unknown key 'nu'"),

@@ -27,7 +27,7 @@ from conftest import PKG, ROOT
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import param_schedule_cases as pc             # noqa: E402
-from helpers import rel                       # noqa: E402
+from helpers import _tiny, rel                # noqa: E402
 
 NAMES = list(pc.NAMES)
 
@@ -86,13 +86,6 @@ def test_launch_arguments_end_with_the_three_schedule_words():
 
 
 # ------------------------------------------------------------------------------------------------ Python validation
-def _tiny(**kw):
-    from mgadmm.ADMM import ADMM_algorithm
-    cl = torch.tensor([[0, 1], [1, 0]])
-    return ADMM_algorithm({"n_nodes": 2}, dict(rho=1, rho_u=1, rho_d=1, mu_u=1, mu_d1=1, mu_d2=1), use_kNN=True,
-                          u_sigma=1.0, d_sigma=1.0, tables=(cl, torch.tensor([[0.0, 1.0], [0.0, 1.0]])), **kw)
-
-
 ONES = np.ones((4, 3))
 
 

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import PKG, ROOT
+from helpers import _tiny
 
 LIB = os.path.join(PKG, "mgadmm", "libmgadmm.so")
 NAMES = ["rho", "rho_u", "rho_d", "mu_u", "mu_d1", "mu_d2"]
@@ -73,13 +74,6 @@ def test_one_pp_instance_per_default_instance():
     ps = set(re.findall(r"__device_stub__k_admm_lds_ps(<[^>]*>)", out))
     assert len(base) == 45 and pp == base, dict(missing=sorted(base - pp), extra=sorted(pp - base))
     assert ps == base
-
-
-def _tiny(**kw):
-    from mgadmm.ADMM import ADMM_algorithm
-    cl = torch.tensor([[0, 1], [1, 0]])
-    return ADMM_algorithm({"n_nodes": 2}, dict(rho=1, rho_u=1, rho_d=1, mu_u=1, mu_d1=1, mu_d2=1), use_kNN=True,
-                          u_sigma=1.0, d_sigma=1.0, tables=(cl, torch.tensor([[0.0, 1.0], [0.0, 1.0]])), **kw)
 
 
 BAD = [
