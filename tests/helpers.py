@@ -99,13 +99,17 @@ def finite_termination(h, nm, n_it):
     return out
 
 
-def check_windows(tag, blk, x, idx, o, xo, xtol=1e-5, htol=1e-3, slack=1, abl="None", finite_termination_rule=False):
+def check_windows(tag, blk, x, idx, o, xo, xtol=1e-5, htol=1e-3, slack=1, abl="None", finite_termination_rule=False, ldr_allow=0.0):
     """GPU batch result `x` (+ blk.metrics_per_sample, blk.CG_iter_*) against the oracle run on windows `idx`.
     Tolerances of the BASELINE configs (float32 kernels vs the float64 oracle): x per sample, every history list, CG counts
     (the diagonal x solve of 'DGTV' / 'UT' gets the +-2 of check_solve in test_gpu_parity.py).
     finite_termination_rule: a solve whose float64 count is a finite-termination count (finite_termination) may also lie
     in [ref - 1, 2 ref + 1], the bound test_gpu_random.py sets for such counts: float32 loses the exact termination and
-    runs on until its recursive residual passes the tolerance."""
+    runs on until its recursive residual passes the tolerance.
+    ldr_allow: E, the largest rounding error of an entry of Ldr x in the solver's format (tests/prox_cases.py: E_l).  On smooth
+    data Ldr x is small against ||x||, and the quantities that are functions of it get E on top of their tolerance: a norm over
+    M entries (the phi pair of the residual lists) sqrt(M) E, the sum of |Ldr x| (DGTV) E per entry, and the sum of squares
+    (DGLR), a squared norm n^2, d (2 n + d) with d = sqrt(M) E.  0 (the default) changes nothing."""
     from mgadmm import _lib as L
     has_phi, has_zd = abl in ("None", "DGLR"), abl != "DGLR"
     idx = np.asarray(idx)
@@ -125,15 +129,22 @@ def check_windows(tag, blk, x, idx, o, xo, xtol=1e-5, htol=1e-3, slack=1, abl="N
     res = [(L.M_PRI_ZU, L.M_DUAL_ZU)] + [(L.M_PRI_PHI, L.M_DUAL_PHI)] * has_phi + [(L.M_PRI_ZD, L.M_DUAL_ZD)] * has_zd
     pri = np.stack([norm(p) for p, _ in res], 1)
     dual = np.stack([norm(d) for _, d in res], 1)
-    np.testing.assert_allclose(pri, np.array(h.p_res_list), rtol=htol, atol=floor, err_msg=f"{tag} primal residuals")
-    np.testing.assert_allclose(dual, np.array(h.d_res_list), rtol=htol, atol=floor, err_msg=f"{tag} dual residuals")
+    per_window = xo[0].size                                   # entries of one window
+    at = np.full(len(res), floor)
+    if has_phi:
+        at[1] += np.sqrt(per_window * len(idx)) * ldr_allow
+    for j in range(len(res)):
+        np.testing.assert_allclose(pri[:, j], np.array(h.p_res_list)[:, j], rtol=htol, atol=at[j], err_msg=f"{tag} primal residuals, column {j}")
+        np.testing.assert_allclose(dual[:, j], np.array(h.d_res_list)[:, j], rtol=htol, atol=at[j], err_msg=f"{tag} dual residuals, column {j}")
     np.testing.assert_allclose(norm(L.M_XSHIFT), np.array(h.x_shift_list), rtol=htol, atol=floor, err_msg=f"{tag} x shift")
     np.testing.assert_allclose(norm(L.M_RECOVER), np.array(h.recover_list), rtol=htol, atol=floor, err_msg=f"{tag} ||Hx-y||")
     np.testing.assert_allclose(mean(L.M_GLR), np.array(h.GLR_list), rtol=htol, err_msg=f"{tag} GLR")
     if has_phi:
-        np.testing.assert_allclose(mean(L.M_DGTV), np.array(h.DGTV_list), rtol=htol, err_msg=f"{tag} DGTV")
+        np.testing.assert_allclose(mean(L.M_DGTV), np.array(h.DGTV_list), rtol=htol, atol=per_window * ldr_allow, err_msg=f"{tag} DGTV")
     if has_zd:
-        np.testing.assert_allclose(mean(L.M_DGLR), np.array(h.DGLR_list), rtol=htol, err_msg=f"{tag} DGLR")
+        d = np.sqrt(per_window) * ldr_allow
+        for i, (g, r) in enumerate(zip(mean(L.M_DGLR), h.DGLR_list)):
+            np.testing.assert_allclose(g, r, rtol=htol, atol=d * (2 * np.sqrt(r) + d), err_msg=f"{tag} DGLR, iteration {i}")
     for nm in ("CG_iter_x", "CG_iter_zu") + ("CG_iter_zd",) * has_zd:
         got = torch.stack(getattr(blk, nm)).numpy()[:, idx]
         ref = np.array(getattr(h, nm)).reshape(n_it, -1)
