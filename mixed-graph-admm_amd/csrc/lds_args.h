@@ -102,9 +102,25 @@ int mg_lds_init(bool masked, int T, int t_in, int N, int TPG, int B, float tm, f
 // row_of_node (device, [N]; nullptr = identity): the thread-major vectors are in ROW order (the thread of row r owns node
 // node_of_row[r]), what a caller imports / exports stays in node order
 int mg_lds_state_layout(bool to_thread_major, int T, int N, int TPG, int B, const float* src, float* dst, const int* row_of_node, hipStream_t st);
-// delta_x_per_step on the sample-major layout (ADMM.py:614): scratch = double[TN * (1 + ceil(B/64))], out = double[T];
-// stop: device stop word (the kernels return at once when it is set) or nullptr
-int mg_lds_dxps(int T, int N, int B, const float* x, const float* xo, double* scratch, double* out, const int* stop, hipStream_t st);
+// The whole-batch metrics of one ADMM iteration in two launches (k_lds_metric_pass, k_lds_metric_final): delta_x_per_step on
+// the sample-major layout (ADMM.py:614) and the whole-batch value of every metric from the per-sample sums (ADMM.py:612-637)
+struct LdsMetricArgs {
+    int T, N, B, Bp;
+    const float *x, *xo;       // iterate k + 1 and iterate k, (B, T*N)
+    double* scratch;           // double[T*N * ceil(B/64)]: the sums of every 64-sample slice
+    double* dxps;              // double[T]
+    const int* stop;           // device stop word (the delta_x_per_step half returns at once when it is set) or nullptr
+    const double* ps;          // [NMETRIC][Bp] per-sample sums
+    double* out;               // [NMETRIC]
+    double* out_ps;            // [NMETRIC][B] copy of the sums, or nullptr
+};
+// How the two launches are cut into workgroups.  Beside a k_admm_lds launch (busy) only single waves find room on a CU, and
+// the fewer CUs they touch the better; on an idle GPU the pass takes one task per thread and the whole device
+struct LdsMetricShape {
+    int threads;               // per workgroup: 64, 256 or 512
+    int wgs;                   // workgroups of the pass, 0: one task per thread
+};
+int mg_lds_metrics(const LdsMetricArgs& a, const LdsMetricShape& shape, hipStream_t st);
 // History of a solve that stopped per sample, from the stop words and the per-sample metric sums ps = [n_it][NMETRIC][Bp] of
 // all n_it iterations enqueued: n_per_sample[b] = n_b (max_it for a sample that never stopped); metrics[n_it][NMETRIC] = the
 // whole-batch values as if a stopped sample stood still (difference terms 0, the others as at its last iteration);

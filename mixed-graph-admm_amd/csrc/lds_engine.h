@@ -3,6 +3,8 @@
 // on that path (solve_lds, the one virtual Engine::solve calls).  What decides -- the plan, the schedule, the refusals -- is
 // in lds_plan.h, lds_schedule.h and solve_gate.h; this drives the HIP calls.  Included by solver_f32.hip only.
 #pragma once
+#include <stdio.h>
+
 #include <thread>
 
 #include "engine.h"
@@ -15,7 +17,9 @@ namespace {
 struct LdsEngine final : Engine<float> {
     int dev_cus = 0;               // compute units of the device (staggered start of k_admm_lds)
     int* d_lds_csr = nullptr;
-    double* d_m2 = nullptr;
+    double* d_slice_sums = nullptr;   // [ceil(Bmax/64)][T*N]: delta_x_per_step, the sums of x - x_old over every 64-sample slice
+    // the whole-batch metric kernels (lds_args.h, mg_lds_metrics) beside a k_admm_lds launch and on an idle GPU
+    LdsMetricShape metric_busy{64, 0}, metric_idle{256, 0};
     // ADMM outer loop of the LDS path without host round trips (solve_lds): device stop word, second metric buffer, helper
     // stream for the whole-batch metric kernels and the events that order the two streams
     int lds_async = 1;            // MGADMM_LDS_ASYNC=0: one stream, the host tests the stop criterion after every iteration
@@ -58,7 +62,7 @@ struct LdsEngine final : Engine<float> {
     ~LdsEngine() override {
         (void)hipSetDevice(g->device);
         auto fr = [](void* q) { if (q) (void)hipFree(q); };
-        fr(d_lds_csr); fr(d_m2); fr(d_stop); fr(d_ps_ring); fr(d_pstop); fr(d_ps_full);
+        fr(d_lds_csr); fr(d_slice_sums); fr(d_stop); fr(d_ps_ring); fr(d_pstop); fr(d_ps_full);
         fr(d_sp); fr(d_sg_img); fr(d_sg_set); fr(d_sch); fr(d_ad_tab); fr(d_ad_w); fr(d_ad_hist);
         for (float* b : lds_ring_extra) if (b) (void)hipFree(b);
         if (st_side) (void)hipStreamDestroy(st_side);
@@ -191,7 +195,12 @@ struct LdsEngine final : Engine<float> {
         MG_HIP(hipMalloc(&d_lds_csr, sizeof(int) * img.size()));
         MG_HIP(hipMemcpy(d_lds_csr, img.data(), sizeof(int) * img.size(), hipMemcpyHostToDevice));
         lds_img_host = img;
-        MG_HIP(hipMalloc(&d_m2, sizeof(double) * T * N * (1 + (size_t)(Bmax + 63) / 64)));
+        MG_HIP(hipMalloc(&d_slice_sums, sizeof(double) * T * N * ((size_t)(Bmax + 63) / 64)));
+        // MGADMM_LDS_METRIC_SHAPE=<threads>x<workgroups> (workgroups 0: one task per thread): the busy shape, for experiments
+        if (const char* e = getenv("MGADMM_LDS_METRIC_SHAPE")) {
+            int nt = 0, wgs = 0;
+            if (sscanf(e, "%dx%d", &nt, &wgs) == 2 && (nt == 64 || nt == 256 || nt == 512) && wgs >= 0) metric_busy = LdsMetricShape{nt, wgs};
+        }
         MG_HIP(hipMalloc(&d_stop, sizeof(int)));
         MG_HIP(hipMemset(d_stop, 0, sizeof(int)));
         MG_HIP(hipMalloc(&d_ps_ring, sizeof(double) * LDS_SETS * LDS_MAXJ * MGADMM_NMETRIC * Bp_max));
@@ -322,14 +331,17 @@ struct LdsEngine final : Engine<float> {
         return out(so->gamma_d, a.gd);
     }
 
-    // the whole-batch metrics of iteration `it` (delta_x_per_step, norms / means over the samples) on stream `s`
-    int lds_batch_metrics(const LdsRun& r, int it, const double* ps, hipStream_t s) {
+    // the whole-batch metrics of iteration `it` (delta_x_per_step, norms / means over the samples) on stream `s`: two launches;
+    // busy: a k_admm_lds launch runs beside them (the helper stream of CHUNKS while the caller's stream has launches left)
+    int lds_batch_metrics(const LdsRun& r, int it, const double* ps, hipStream_t s, bool busy) {
         const bool per_sample = r.hist && r.hist->metrics_per_sample;
-        MG_TRY(mg_lds_dxps(T, N, r.B, lds_xbuf(r, it + 1), lds_xbuf(r, it), d_m2, d_dxps + (size_t)it * T, r.a.stop, s));
-        hipLaunchKernelGGL(k_batch_metrics, dim3(MGADMM_NMETRIC), dim3(256), 0, s, ps, r.Bp, r.B, d_hist + (size_t)it * MGADMM_NMETRIC,
-                           per_sample ? d_hist_ps + (size_t)it * MGADMM_NMETRIC * r.B : nullptr);
-        MG_HIP(hipGetLastError());
-        return MGADMM_OK;
+        LdsMetricArgs m;
+        m.T = T; m.N = N; m.B = r.B; m.Bp = r.Bp;
+        m.x = lds_xbuf(r, it + 1); m.xo = lds_xbuf(r, it);
+        m.scratch = d_slice_sums; m.dxps = d_dxps + (size_t)it * T; m.stop = r.a.stop;
+        m.ps = ps; m.out = d_hist + (size_t)it * MGADMM_NMETRIC;
+        m.out_ps = per_sample ? d_hist_ps + (size_t)it * MGADMM_NMETRIC * r.B : nullptr;
+        return mg_lds_metrics(m, busy ? metric_busy : metric_idle, s);
     }
 
     // The host's late look at a device word (the stop word, the number of stopped samples): after step `c` the word is copied
@@ -416,7 +428,9 @@ struct LdsEngine final : Engine<float> {
             // c + 1; the first launch that writes the set again is launch c + 3 on the same stream, so the hazard rule of
             // lds_schedule.h holds as it stands (the metric kernels beside it only read the set)
             MG_TRY(adapt_step(r, ch.it0 + ch.Jc - 1, a.ps + (size_t)(ch.Jc - 1) * row));
-            for (int k = 0; k < ch.Jc; ++k) MG_TRY(lds_batch_metrics(r, ch.it0 + k, a.ps + (size_t)k * row, st_side));
+            // (after the last chunk the caller's stream has nothing left: its metrics take the whole GPU)
+            const bool busy = c + 1 < r.s.chunks();
+            for (int k = 0; k < ch.Jc; ++k) MG_TRY(lds_batch_metrics(r, ch.it0 + k, a.ps + (size_t)k * row, st_side, busy));
             MG_HIP(hipEventRecord(ev_side[ch.ev], st_side));
             r.n_done = ch.it0 + ch.Jc;
         }
@@ -442,7 +456,7 @@ struct LdsEngine final : Engine<float> {
             }
             MG_TRY(launch_lds(a, r.B));
             MG_TRY(adapt_step(r, it, a.ps));
-            if (!r.s.per_sample) MG_TRY(lds_batch_metrics(r, it, a.ps, st));
+            if (!r.s.per_sample) MG_TRY(lds_batch_metrics(r, it, a.ps, st, false));
             if (r.record) {
                 for (int w = 0; w < 3; ++w)
                     if (w < 2 || r.has_zd) MG_TRY(save_coeffs(r.Bp, r.hist, it, w, r.B, w));

@@ -1,6 +1,7 @@
 // LDS-resident fused ADMM path: kernel instantiations and launches (own translation unit: the library builds in parallel).
 #define MG_LDS_UNIT 0     // MGADMM_Q_LDS_UNIT: this unit's launches report the kernels k_admm_lds
 #include "lds_dispatch.h"
+#include "lds_metric_kernels.h"
 
 int mg_lds_iteration(const LdsLaunch& L, const LdsArgs& a, int B, hipStream_t st) {
     // a launch that carries per-sample weights takes the instances that read them (lds_launch_pp.hip),
@@ -26,14 +27,27 @@ int mg_lds_state_layout(bool to_thread_major, int T, int N, int TPG, int B, cons
     return MGADMM_OK;
 }
 
-int mg_lds_dxps(int T, int N, int B, const float* x, const float* xo, double* scratch, double* out, const int* stop, hipStream_t st) {
-    const int TN = T * N, nsl = (B + 63) / 64;
-    if (TN % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)xo % 16) == 0)
-        hipLaunchKernelGGL(k_dxps_sm4, dim3((TN / 4 + 63) / 64, nsl), dim3(64), 0, st, TN, B, x, xo, scratch + TN, stop);
-    else
-        hipLaunchKernelGGL(k_dxps_sm, dim3((TN + 255) / 256, nsl), dim3(256), 0, st, TN, B, x, xo, scratch + TN, stop);
-    hipLaunchKernelGGL(k_dxps_sm_mean, dim3((TN + 255) / 256), dim3(256), 0, st, TN, B, nsl, (const double*)(scratch + TN), scratch, stop);
-    hipLaunchKernelGGL(k_dxps_sm_final, dim3(T), dim3(256), 0, st, T, N, (const double*)scratch, out, stop);
+template <int NT>
+static void lds_metrics_launch(const LdsMetricArgs& a, int wgs, hipStream_t st) {
+    const int TN = a.T * a.N, nsl = (a.B + 63) / 64;
+    const bool vec4 = TN % 4 == 0 && ((uintptr_t)a.x % 16) == 0 && ((uintptr_t)a.xo % 16) == 0;
+    const long long tasks = (long long)(vec4 ? TN / 4 : TN) * nsl;
+    const long long full = (tasks + NT - 1) / NT;
+    const int grid = (int)(wgs > 0 && wgs < full ? wgs : full);
+    if (vec4) hipLaunchKernelGGL((k_lds_metric_pass<4, NT>), dim3(grid), dim3(NT), 0, st, TN, a.B, a.x, a.xo, a.scratch, a.stop);
+    else hipLaunchKernelGGL((k_lds_metric_pass<1, NT>), dim3(grid), dim3(NT), 0, st, TN, a.B, a.x, a.xo, a.scratch, a.stop);
+    constexpr int NF = NT < 256 ? NT : 256;      // (the tree of the final has 256 leaves)
+    hipLaunchKernelGGL((k_lds_metric_final<NF>), dim3(a.T + MGADMM_NMETRIC), dim3(NF), 0, st, a.T, a.N, a.B, a.Bp, nsl,
+                       (const double*)a.scratch, a.dxps, a.stop, a.ps, a.out, a.out_ps);
+}
+
+int mg_lds_metrics(const LdsMetricArgs& a, const LdsMetricShape& shape, hipStream_t st) {
+    switch (shape.threads) {
+        case 64: lds_metrics_launch<64>(a, shape.wgs, st); break;
+        case 256: lds_metrics_launch<256>(a, shape.wgs, st); break;
+        case 512: lds_metrics_launch<512>(a, shape.wgs, st); break;
+        default: mg_set_error("lds: metric pass with workgroups of %d threads (64, 256 or 512)", shape.threads); return MGADMM_ERR_INVALID;
+    }
     MG_HIP(hipGetLastError());
     return MGADMM_OK;
 }
