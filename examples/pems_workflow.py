@@ -164,6 +164,24 @@ def main():
           f"rho, rho_u, rho_d of window 0 at the end: " + ", ".join(f"{v:.3g}" for v in blk.rho_final[:, 0])
           + f" (start: {admm_info['rho']:.3g}, {admm_info['rho_u']:.3g}, {admm_info['rho_d']:.3g})")
 
+    # the grid search the reference's authors call their main finding is over the temporal graph itself: the largest
+    # skip-connection interval of the line graph, 1 ... 6 (one instance, one graph and one solve per value there).  Here ONE
+    # line-graph instance of width 6 and ONE batch: 6 intervals x 2 values of mu_d1 on the same windows, every sample reading the
+    # band table of its interval (a narrower interval is the width-6 table with zero hops)
+    line = ADMM_algorithm(ds.graph_info, admm_info, use_kNN=True, k=4, u_sigma=50, use_line_graph=True, skip_connection=6)
+    line.max_ADMM_iter, line.admm_convergence = args.iters, "per_sample"
+    skips, mus = [1, 2, 3, 4, 5, 6], [admm_info["mu_d1"], 2 * admm_info["mu_d1"]]
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    xs, n_it, sets = line.sweep(y[:nw], {"mu_d1": mus}, skips=skips)      # (12, nw, 24, N, 1); sets: mu_d1 slowest, 'skip' fastest
+    torch.cuda.synchronize(); dt = time.perf_counter() - t0
+    mae = [(ds.recover_data(xs[p][:, 12:]) - truth).abs().mean().item() for p in range(len(sets))]
+    print(f"skip-connection sweep: {len(sets)} cells x {nw} windows x {int(n_it.max())} ADMM iterations in {dt * 1e3:.1f} ms; "
+          "MAE of the 12 predicted steps / mean ADMM iterations")
+    print("  mu_d1 \\ skip " + "".join(f"{s:>14d}" for s in skips))
+    for i, m in enumerate(mus):
+        print(f"  {m:>12.3g} " + "".join(f"{mae[i * 6 + j]:>8.3f} /{n_it[i * 6 + j].mean():>4.0f}" for j in range(6)))
+    line.close()
+
     ix, iy, mask = ds.get_interpolated_batch(starts, 0.4)
     blk._reset_history()
     x_int = blk.combined_loop(iy, mask=mask, print_info=False)

@@ -159,7 +159,7 @@ typedef struct mgadmm_solver mgadmm_solver;
  * n_iters_per_sample): a caller built against an older header must be rebuilt -- compare the string before passing structs.
  * The patch number counts additions that leave every struct alone (0.3.1: mgadmm_solver_set_sample_params;
  * 0.3.2: mgadmm_solver_set_sample_graphs; 0.3.3: mgadmm_solver_set_param_schedule;
- * 0.3.4: mgadmm_solver_set_adaptive_rho, mgadmm_solver_get_adaptive_history). */
+ * 0.3.4: mgadmm_solver_set_adaptive_rho, mgadmm_solver_get_adaptive_history; 0.3.5: mgadmm_solver_set_sample_bands). */
 const char* mgadmm_version(void);
 const char* mgadmm_last_error(void);
 
@@ -276,6 +276,28 @@ int mgadmm_solver_set_adaptive_rho(mgadmm_solver* s, const mgadmm_adaptive_rho* 
  * values after step p (the last row of a solve that ends on a step is what a resumed solve starts with).  NaN past a
  * sample's own stop (per-sample stop).  Another B than the solve's -> MGADMM_ERR_INVALID. */
 int mgadmm_solver_get_adaptive_history(mgadmm_solver* s, int32_t B, double* rho_hist, int32_t max_periods, int32_t* n_periods);
+/* Per-sample temporal band weights: sample b of the following mgadmm_solve / mgadmm_solve_from calls with this B reads the band
+ * table band_w[set_of_sample[b]] instead of the graph's own (mgadmm_graph_desc::band_w): a sweep over the skip-connection
+ * interval of the line graph -- or over arbitrary hop weights -- on W windows as one batch.  `band_w`: n_sets tables [T][skip]
+ * of floats, row t = the weights of x[t-1-s], with the T and the skip (the WIDTH) of the solver's graph; a narrower interval is
+ * a table of that width whose further hops are 0, and its samples equal, bit for bit, the solve by a solver created on a graph
+ * of the narrow width.  set_of_sample: host int32[B].  Both arrays are copied.  n_sets == 0 or a NULL pointer clears the table.
+ * mgadmm_solver_set_params keeps it.  Only entries with s < min(t, skip) are ever read, as with the graph's own table; the
+ * others are ignored.  Synchronous (it waits for the device before an old table is freed).
+ *   - a graph that is not MGADMM_TEMPORAL_BAND -> MGADMM_ERR_UNSUPPORTED;
+ *   - B outside [1, max_batch], n_sets outside [1, max_batch], a set_of_sample[b] outside [0, n_sets) (the message names the
+ *     sample), a read entry that is not finite (the message names [set][t][s]) -> MGADMM_ERR_INVALID.
+ * While a table is set (decided when a solve starts, after every refusal of the tables above and before anything runs; the
+ * messages contain "sample_bands"): a solve with another B -> MGADMM_ERR_INVALID; check_stop = 1 with MGADMM_ADMM_WHOLE_BATCH
+ * -> MGADMM_ERR_UNSUPPORTED (the samples solve different problems): run a fixed count or stop per sample.
+ *   - LDS-resident float32 path: the launches take the kernels k_admm_lds_pp (MGADMM_Q_LDS_UNIT = 2); alone or together with
+ *     mgadmm_solver_set_sample_params, the per-sample param_schedule, adaptive_rho and the per-sample stop;
+ *   - streaming path (float32 and float64, either cg_convergence): a fixed iteration count (the per-sample stop does not exist
+ *     there); the kernels read a weight per batch column.
+ * SCOPE: mgadmm_solve / mgadmm_solve_from only.  mgadmm_two_loops and the fine-grained entry points (mgadmm_apply, mgadmm_lhs,
+ * mgadmm_cg, mgadmm_phi_direct) IGNORE the table: they keep reading the graph's own band table. */
+int mgadmm_solver_set_sample_bands(mgadmm_solver* s, int32_t n_sets, const float* band_w /* [n_sets][T][skip] */,
+                                   const int32_t* set_of_sample /* [B] */, int32_t B);
 /* bytes of device workspace held by the solver */
 int64_t mgadmm_solver_workspace_bytes(const mgadmm_solver* s);
 /* which path (MGADMM_PATH_STREAM / MGADMM_PATH_LDS) a batch of size B would take */

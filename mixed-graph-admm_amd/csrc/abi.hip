@@ -66,6 +66,11 @@ int mgadmm_solver_set_adaptive_rho(mgadmm_solver* s, const mgadmm_adaptive_rho* 
     return s->eng->set_adaptive_rho(ar, start);
 }
 
+int mgadmm_solver_set_sample_bands(mgadmm_solver* s, int32_t n_sets, const float* band_w, const int32_t* set_of_sample, int32_t B) {
+    MG_REQUIRE(s, "set_sample_bands: null solver");
+    return s->eng->set_sample_bands(n_sets, band_w, set_of_sample, B);
+}
+
 int mgadmm_solver_get_adaptive_history(mgadmm_solver* s, int32_t B, double* rho_hist, int32_t max_periods, int32_t* n_periods) {
     MG_REQUIRE(s, "get_adaptive_history: null solver");
     return s->eng->get_adaptive_history(B, rho_hist, max_periods, n_periods);

@@ -57,6 +57,7 @@ struct OpDesc {
     int self_mode;        // SelfMode
     int q1;               // SELF_LDRT: keep the identity on the t=0 block (quirk Q1)
     const double* self_w; // optional per-row factor of the self coefficient (apply_op_Ln: row sums of d_ew); plain row kernel only
+    const float* band_wb; // BAND, optional: [T*skip][Bp] a weight per batch column (mgadmm_solver_set_sample_bands) instead of band_w
 };
 
 struct mgadmm_graph {
@@ -100,6 +101,7 @@ struct EngineBase {
     virtual int set_sample_graphs(int n_sets, mgadmm_graph* const* graphs, const int32_t* set_of_sample, int B) = 0;
     virtual int set_param_schedule(const mgadmm_param_schedule* sch, int n_rows, int B, int first_row) = 0;
     virtual int set_adaptive_rho(const mgadmm_adaptive_rho* ar, int start) = 0;
+    virtual int set_sample_bands(int n_sets, const float* band_w, const int32_t* set_of_sample, int B) = 0;
     virtual int get_adaptive_history(int B, double* rho_hist, int max_periods, int* n_periods) = 0;
     virtual int64_t workspace_bytes() const = 0;
     virtual int path_for(int B) const = 0;

@@ -21,6 +21,7 @@
 #include "lds_plan.h"
 #include "lds_param_table.h"
 #include "solve_gate.h"
+#include "band_sets.h"
 
 namespace {
 
@@ -90,6 +91,13 @@ struct Engine : EngineBase {
     int ad_start = 0;
     int ad_last_periods = 0;         // of the last solve (mgadmm_solver_get_adaptive_history); 0 periods: it did not adapt
     int sg_B = 0;                    // samples of the graph table (mgadmm_solver_set_sample_graphs); 0: none set
+    // per-sample temporal band weights (mgadmm_solver_set_sample_bands, band_sets.h): the caller's tables, and for the streaming
+    // kernels their expansion to a weight per batch column, [T*skip][bs_Bp] floats for the geometry of a solve of bs.B samples.
+    // band_wb: non-null only while a solve with the table runs -- the fine-grained entry points and two_loops read the graph's own table
+    bandsets::BandSets bs;
+    float* d_bs_exp = nullptr;
+    int bs_Bp = 0;
+    const float* band_wb = nullptr;
     StreamKeyLog stream_keys;        // MGADMM_Q_STREAM_KEYS / _KEY0 + i: distinct k_rows / k_tile / k_cldr instances launched (stream_keys.h)
     static constexpr bool IS_F64 = std::is_same<S, double>::value;
     // profiling
@@ -113,7 +121,7 @@ struct Engine : EngineBase {
         auto fr = [](void* q) { if (q) (void)hipFree(q); };
         fr(vec_pool); fr(partials); fr(d_rr); fr(d_alpha); fr(d_beta); fr(d_alpha_hist); fr(d_beta_hist);
         fr(d_active); fr(d_iters_tmp); fr(d_nact); fr(d_nonfinite); fr(d_ps); fr(d_hist); fr(d_dxps);
-        fr(d_dxpart); fr(d_hist_ps); fr(d_cg_iters);
+        fr(d_dxpart); fr(d_hist_ps); fr(d_cg_iters); fr(d_bs_exp);
         for (auto& tmd : tmeta) { fr(tmd.tl_col); fr(tmd.tl_w); fr(tmd.halo); fr(tmd.h_rowptr); fr(tmd.h_col); fr(tmd.h_val); }
         fr(cldr_dev.n0); fr(cldr_dev.nC); fr(cldr_dev.rows); fr(cldr_dev.dcol); fr(cldr_dev.dcnt); fr(cldr_dev.tcol); fr(cldr_dev.tcnt);
         fr(cldr_dev.dw); fr(cldr_dev.tw);
@@ -535,6 +543,34 @@ struct Engine : EngineBase {
         return refused(solvegate::set_sample_graphs_gate(facts(p)));
     }
 
+    // ---------------------------------------------------------------- per-sample temporal band weights
+    // Sample b reads the band table of set set_of_sample[b] (band_sets.h: the checks, the caller's arrays).  Here also the table
+    // of the streaming kernels, a weight per batch column of the geometry a solve of B samples gets; LdsEngine adds the tables
+    // of the LDS path.  Synchronous: an old table is freed after the device has finished whatever read it
+    int set_sample_bands(int n_sets, const float* band_w, const int32_t* set_of_sample, int B) override {
+        MG_HIP(hipSetDevice(g->device));
+        MG_TRY(refused(bs.set(g->mode == MGADMM_TEMPORAL_BAND, T, g->skip, n_sets, band_w, set_of_sample, B, Bmax)));
+        MG_HIP(hipDeviceSynchronize());
+        if (d_bs_exp) (void)hipFree(d_bs_exp);
+        d_bs_exp = nullptr;
+        bs_Bp = 0;
+        if (bs.B == 0) return MGADMM_OK;
+        std::vector<float> exp;
+        const int Bp = make_geom(bs.B).Bp;
+        bs.expand(Bp, exp);
+        if (hipMalloc(&d_bs_exp, sizeof(float) * exp.size()) != hipSuccess ||
+            hipMemcpy(d_bs_exp, exp.data(), sizeof(float) * exp.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            if (d_bs_exp) (void)hipFree(d_bs_exp);
+            d_bs_exp = nullptr;
+            bs.clear();
+            mg_set_error("set_sample_bands: upload of the expanded table failed");
+            return MGADMM_ERR_HIP;
+        }
+        bs_Bp = Bp;
+        return MGADMM_OK;
+    }
+
     int64_t workspace_bytes() const override { return ws_bytes; }
     int path_for(int) const override { return use_lds() ? MGADMM_PATH_LDS : MGADMM_PATH_STREAM; }
     // the fused LDS kernel runs one sample per workgroup with its CG loops inside: a batch-global stop cannot be expressed there
@@ -784,6 +820,9 @@ struct Engine : EngineBase {
         return MGADMM_OK;
     }
 
+    // Ldr / Ldr^T as a solve reads them: the graph's, with the per-column band weights while a solve with a band table runs
+    OpDesc op_ldr() const { OpDesc o = g->op_ldr(); o.band_wb = band_wb; return o; }
+    OpDesc op_ldrt() const { OpDesc o = g->op_ldrt(); o.band_wb = band_wb; return o; }
     static OpDesc op_none() {
         OpDesc o{};
         o.kind = OPK_NONE;
@@ -861,8 +900,8 @@ struct Engine : EngineBase {
             // one launch = two SpMM applications (Ldr, Ldr^T): 2 x 8 B/element algorithmic
             if (cldr_fits(q))
                 return rows_cldr<EpiLhs>(q, pin, live, 0, 4, (const S*)nullptr, mask, Ap, d.hth, p.t_in, (S)d.c1, (S)d.c2);
-            MG_TRY(rows<EpiStore>(q, g->op_ldr(), pin, live, 0, 2, vec[V_Q]));
-            return rows<EpiLhs>(q, g->op_ldrt(), vec[V_Q], live, 0, 3, pin, mask, Ap, d.hth, p.t_in, (S)d.c1, (S)d.c2);
+            MG_TRY(rows<EpiStore>(q, op_ldr(), pin, live, 0, 2, vec[V_Q]));
+            return rows<EpiLhs>(q, op_ldrt(), vec[V_Q], live, 0, 3, pin, mask, Ap, d.hth, p.t_in, (S)d.c1, (S)d.c2);
         }
         if (d.kind == 2)
             return rows<EpiLhs>(q, g->op_lu(), pin, live, 0, 2, (const S*)nullptr, mask, Ap, d.hth, p.t_in, (S)d.c1, (S)d.c2);
@@ -890,8 +929,8 @@ struct Engine : EngineBase {
         if (d.kind == 1 && cldr_fits(q)) {
             MG_TRY(rows_cldr<EpiCgInit>(q, x0, nullptr, 2, 7, (const S*)nullptr, rhs, mask, r, pp, xout, d.hth, p.t_in, (S)d.c1, (S)d.c2));
         } else if (d.kind == 1) {
-            MG_TRY(rows<EpiStore>(q, g->op_ldr(), x0, nullptr, 2, 2, vec[V_Q]));
-            MG_TRY(rows<EpiCgInit>(q, g->op_ldrt(), vec[V_Q], nullptr, 2, 6, x0, rhs, mask, r, pp, xout, d.hth, p.t_in,
+            MG_TRY(rows<EpiStore>(q, op_ldr(), x0, nullptr, 2, 2, vec[V_Q]));
+            MG_TRY(rows<EpiCgInit>(q, op_ldrt(), vec[V_Q], nullptr, 2, 6, x0, rhs, mask, r, pp, xout, d.hth, p.t_in,
                                    (S)d.c1, (S)d.c2));
         } else if (d.kind == 2) {
             MG_TRY(rows<EpiCgInit>(q, g->op_lu(), x0, nullptr, 2, 5, (const S*)nullptr, rhs, mask, r, pp, xout, d.hth,
@@ -1173,7 +1212,7 @@ struct Engine : EngineBase {
         // ---- RHS_x (ADMM.py:556-564)
         if (has_phi) {
             MG_TRY(rows<EpiLin2>(q, op_none(), vec[V_GAM], nullptr, 3, 3, (const S*)vec[b.phc], vec[V_TMP], (S)1, rho));
-            MG_TRY(rows<EpiRhsX>(q, g->op_ldrt(), vec[V_TMP], nullptr, 2, has_zd ? 7 : 5, (const S*)vec[b.zuc],
+            MG_TRY(rows<EpiRhsX>(q, op_ldrt(), vec[V_TMP], nullptr, 2, has_zd ? 7 : 5, (const S*)vec[b.zuc],
                                  (const S*)vec[b.zdc], (const S*)vec[V_GU], (const S*)vec[V_GD], (const S*)vec[V_Y],
                                  vec[V_RHS], rho_u, rho_d, 1, has_zd ? 1 : 0));
         } else {
@@ -1221,9 +1260,16 @@ struct Engine : EngineBase {
         st = s;
         ad_last_periods = 0;
         MG_TRY(refused(solvegate::solve_gate(facts(p), set_state(), B)));      // (before anything is enqueued; its order of refusals: solve_gate.h)
+        MG_TRY(refused(bandsets::solve_gate(bs, facts(p), B)));                // (a band table: after every refusal of solve_gate)
         if (use_lds()) return solve_lds(y, mask, B, x0, state_in, x_out, state_out, hist);
         MG_TRY(refused(solvegate::admm_convergence_gate(facts(p), "solve")));       // (refused at solver_create / set_params already)
         const Geom q = make_geom(B);
+        // a band table: the Ldr / Ldr^T of this solve read a weight per batch column (op_ldr, op_ldrt) until it returns
+        struct BandScope { const float*& wb; ~BandScope() { wb = nullptr; } } band_scope{band_wb};
+        if (bs.B > 0) {
+            MG_REQUIRE(d_bs_exp && bs_Bp == q.Bp, "solve: the sample_bands table was expanded for %d columns, the solve has %d", bs_Bp, q.Bp);
+            band_wb = d_bs_exp;
+        }
         MG_TRY(ensure_partials(q));
         const size_t ne = velems(q);
         const bool has_phi = this->has_phi(), has_zd = this->has_zd();
@@ -1254,7 +1300,7 @@ struct Engine : EngineBase {
             MG_TRY(fill(vec[V_GD], ne, (S)0.1));
             if (has_phi) {
                 MG_TRY(fill(vec[V_GAM], ne, (S)0.1));
-                MG_TRY(op_store(q, g->op_ldr(), vec[b.xc], vec[b.phc]));
+                MG_TRY(op_store(q, op_ldr(), vec[b.xc], vec[b.phc]));
             }
             MG_HIP(hipMemcpyAsync(vec[b.zuc], vec[b.xc], ne * sizeof(S), hipMemcpyDeviceToDevice, st));
             MG_HIP(hipMemcpyAsync(vec[b.zdc], vec[b.xc], ne * sizeof(S), hipMemcpyDeviceToDevice, st));
@@ -1272,7 +1318,7 @@ struct Engine : EngineBase {
             MG_TRY((reduce<6>(q, FinMetrics<6>{d_ps, q.Bp, {MGADMM_M_XSHIFT, MGADMM_M_PRI_ZU, MGADMM_M_DUAL_ZU, has_zd ? MGADMM_M_PRI_ZD : -1,
                                                        has_zd ? MGADMM_M_DUAL_ZD : -1, MGADMM_M_RECOVER}}, nullptr)));
             // ---- phi prox, gamma update, Ldr-based residuals and regularisers (ADMM.py:600-606, 627-637)
-            MG_TRY(rows<EpiPhi>(q, g->op_ldr(), vec[b.xn], nullptr, 2, has_phi ? 5 : 1, (const S*)vec[b.phc], vec[b.phn], vec[V_GAM],
+            MG_TRY(rows<EpiPhi>(q, op_ldr(), vec[b.xn], nullptr, 2, has_phi ? 5 : 1, (const S*)vec[b.phc], vec[b.phn], vec[V_GAM],
                                 rho, (S)(w[4] / w[0]), has_phi ? 1 : 0));
             MG_TRY((reduce<4>(q, FinMetrics<4>{d_ps, q.Bp, {has_phi ? MGADMM_M_PRI_PHI : -1, has_phi ? MGADMM_M_DUAL_PHI : -1,
                                                        has_phi ? MGADMM_M_DGTV : -1, has_zd ? MGADMM_M_DGLR : -1}}, nullptr)));

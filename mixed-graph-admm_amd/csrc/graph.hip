@@ -21,7 +21,7 @@ void mg_set_error(const char* fmt, ...) {
 
 extern "C" const char* mgadmm_last_error(void) { return g_err; }
 // 0.2: mgadmm_params gained cg_convergence, max_inner_iter; 0.3: round-3 LDS path, more mgadmm_query_t codes (no struct change)
-extern "C" const char* mgadmm_version(void) { return "mgadmm 0.3.4 (gfx950)"; }
+extern "C" const char* mgadmm_version(void) { return "mgadmm 0.3.5 (gfx950)"; }
 
 int mg_transpose_csr(const HostCsr& A, HostCsr& At) {
     const int n = A.n, nnz = A.nnz();

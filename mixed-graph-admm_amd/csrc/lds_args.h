@@ -74,6 +74,10 @@ struct LdsArgs : LdsArgsCore {
     // everything else): sp then holds sp_rows rows of records, record row * sp_stride + b, and trip k of the launch reads row
     // sched_row(it0 + k, sp_row0, sp_rows).  Zero (no schedule): every trip reads sp[b]
     int sp_rows{}, sp_row0{}, sp_stride{};   // rows of the table, row of the solve's first iteration, records between two rows
+    // Per-sample temporal band weights (mgadmm_solver_set_sample_bands, band_sets.h; read by the BAND instances of the kernels
+    // k_admm_lds_pp only; behind everything else): band_w then holds the tables of S sets back to back, T * skip floats each, and
+    // workgroup b reads the one of set bset[b]
+    const int* bset{nullptr};    // [Bp] device table, or nullptr: band_w is the graph's own table
 };
 
 // Execution plan of k_admm_lds chosen by ldsplan::make (lds_plan.h)

@@ -48,6 +48,10 @@ struct LdsEngine final : Engine<float> {
     int* d_sg_img = nullptr;      // [sets][img_stride]
     int* d_sg_set = nullptr;      // [Bp_max]
     std::vector<int> lds_img_host;
+    // per-sample temporal band weights (mgadmm_solver_set_sample_bands, band_sets.h; the caller's arrays: Engine::bs): the
+    // tables of the sets back to back and the set of every sample
+    float* d_bs_w = nullptr;      // [sets][T*skip]
+    int* d_bs_set = nullptr;      // [Bp_max]
     ldsplan::Switches lds_sw;
     // iterate buffers of solve_lds by slot number (lds_schedule.h): the 15 workspace vectors this path does not use otherwise
     // hold the LDS_SETS (J - 1) + LDS_NBOUND = 13 slots of J = 4; chunks longer than 4 iterations (up to LDS_MAXJ) get the
@@ -63,7 +67,7 @@ struct LdsEngine final : Engine<float> {
         (void)hipSetDevice(g->device);
         auto fr = [](void* q) { if (q) (void)hipFree(q); };
         fr(d_lds_csr); fr(d_slice_sums); fr(d_stop); fr(d_ps_ring); fr(d_pstop); fr(d_ps_full);
-        fr(d_sp); fr(d_sg_img); fr(d_sg_set); fr(d_sch); fr(d_ad_tab); fr(d_ad_w); fr(d_ad_hist);
+        fr(d_sp); fr(d_sg_img); fr(d_sg_set); fr(d_bs_w); fr(d_bs_set); fr(d_sch); fr(d_ad_tab); fr(d_ad_w); fr(d_ad_hist);
         for (float* b : lds_ring_extra) if (b) (void)hipFree(b);
         if (st_side) (void)hipStreamDestroy(st_side);
         for (auto& e : ev_main) if (e) (void)hipEventDestroy(e);
@@ -176,6 +180,20 @@ struct LdsEngine final : Engine<float> {
         if (d_sg_img) (void)hipFree(d_sg_img);
         d_sg_img = fresh;
         sg_B = B;
+        return MGADMM_OK;
+    }
+
+    // The tables lie back to back as the caller gave them: workgroup b of k_admm_lds_pp reads the one of set d_bs_set[b]
+    int set_sample_bands(int n_sets, const float* band_w, const int32_t* set_of_sample, int B) override {
+        MG_TRY(Engine<float>::set_sample_bands(n_sets, band_w, set_of_sample, B));      // (the checks; synchronises; clears)
+        if (d_bs_w) (void)hipFree(d_bs_w);
+        d_bs_w = nullptr;
+        if (bs.B == 0) return MGADMM_OK;
+        const std::vector<int32_t> set_of = bs.padded_set_of(Bp_max);
+        if (!d_bs_set) MG_HIP(hipMalloc(&d_bs_set, sizeof(int) * (size_t)Bp_max));
+        MG_HIP(hipMalloc(&d_bs_w, sizeof(float) * bs.w.size()));
+        MG_HIP(hipMemcpy(d_bs_w, bs.w.data(), sizeof(float) * bs.w.size(), hipMemcpyHostToDevice));
+        MG_HIP(hipMemcpy(d_bs_set, set_of.data(), sizeof(int) * set_of.size(), hipMemcpyHostToDevice));
         return MGADMM_OK;
     }
 
@@ -544,8 +562,11 @@ struct LdsEngine final : Engine<float> {
         }
         // the table of records the launches read (with one they take the kernels k_admm_lds_pp); trip k of a launch reads
         // row sched_row(it0 + k, sp_row0, sp_rows) of it
-        const solvegate::TableChoice tc = solvegate::table_of(set_state(), wt.sch_row0, s.max_it);
-        if (tc.scalar_records) MG_TRY(upload_sample_params(B));      // (a graph table without a weights table)
+        if (bs.B > 0) {                   // (B == bs.B: bandsets::solve_gate) workgroup b reads the band table of set d_bs_set[b]
+            r.a.band_w = d_bs_w; r.a.bset = d_bs_set;
+        }
+        const solvegate::TableChoice tc = bandsets::table_of(solvegate::table_of(set_state(), wt.sch_row0, s.max_it), bs);
+        if (tc.scalar_records) MG_TRY(upload_sample_params(B));      // (a graph or band table without a weights table)
         switch (tc.table) {
             case solvegate::TABLE_NONE: break;
             case solvegate::TABLE_SAMPLE: r.a.sp = d_sp; break;      // (B == sp_B: solve_gate)

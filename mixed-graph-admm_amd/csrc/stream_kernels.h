@@ -124,25 +124,34 @@ __device__ __forceinline__ Vec<S, VEC> op_apply_band(const Geom& g, const OpDesc
     for (int v = 0; v < VEC; ++v) sum.v[v] = S(0);
     S selfc = S(1);
     if (op.kind == OPK_BAND) {
+        // a weight per batch column (op.band_wb, [T*skip][Bp]: mgadmm_solver_set_sample_bands) or one for all (band_w, [T*skip]):
+        // a run-time branch, uniform over the launch; the same products in the same order either way
+        const float* __restrict__ wb = op.band_wb;
+        // entry e of the table times the row `nv`
+        auto hop = [&](int e, const Vec<S, VEC>& nv) {
+            if (wb != nullptr) {
+                const Vec<float, VEC> wv = ldv<float, VEC>(wb + (size_t)e * g.Bp + col0);
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) sum.v[v] += (S)wv.v[v] * nv.v[v];
+            } else {
+                const S w = (S)band_w[e];
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) sum.v[v] += w * nv.v[v];
+            }
+        };
         if (op.band_dir < 0) {
             selfc = (t >= 1) ? S(1) : S(0);
             for (int s = 0; s < op.skip; ++s) {
                 const int ts = t - 1 - s;
                 if (ts < 0) break;
-                const S w = (S)band_w[t * op.skip + s];
-                const Vec<S, VEC> nv = ldv<S, VEC>(in + ((size_t)ts * g.N + i) * g.Bp + col0);
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) sum.v[v] += w * nv.v[v];
+                hop(t * op.skip + s, ldv<S, VEC>(in + ((size_t)ts * g.N + i) * g.Bp + col0));
             }
         } else {
             selfc = (t > 0) ? S(1) : S(0);
             for (int s = 0; s < op.skip; ++s) {
                 const int ts = t + 1 + s;
                 if (ts >= g.T) break;
-                const S w = (S)band_w[ts * op.skip + s];
-                const Vec<S, VEC> nv = ldv<S, VEC>(in + ((size_t)ts * g.N + i) * g.Bp + col0);
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) sum.v[v] += w * nv.v[v];
+                hop(ts * op.skip + s, ldv<S, VEC>(in + ((size_t)ts * g.N + i) * g.Bp + col0));
             }
         }
     }

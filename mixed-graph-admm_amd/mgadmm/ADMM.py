@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from . import utils as _u
+from .band_args import check_skips
 from .graph import Graph, expand_channels, tables_to_csr
 from .solve_args import (ADAPTIVE_RHO_KEYS, GRAPH_PARAM_NAMES, SAMPLE_PARAM_NAMES, _check_adaptive_rho,  # noqa: F401
                          _check_graph_sets, _check_param_schedule, _check_sample_params, _float64,
@@ -513,7 +514,8 @@ class ADMM_algorithm():
 
     def solve(self, y, mask=None, differential=False, print_info=False, return_state=True, per_sample_history=False,
               warm_start=None, sample_params=None, graph_sets=None, graph_of_sample=None, graph_params=None,
-              param_schedule=None, schedule_start=0, adaptive_rho=None, adaptive_start=0):
+              param_schedule=None, schedule_start=0, adaptive_rho=None, adaptive_start=0, band_params=None, band_sets=None,
+              band_of_sample=None):
         """Run the ADMM loop and return ``(x, (zu, zd), phi, history)``; ``history`` is a dict with the
         same lists that are also stored on the instance (p_res_list, d_res_list, ...).
 
@@ -549,9 +551,19 @@ class ADMM_algorithm():
         rho, rho_u, rho_d by period (row 0 the start values; NaN past a sample's own stop) and ``self.rho_final`` (3, B) the last
         values of every sample.  A resumed solve passes ``rho_final`` as ``sample_params`` and ``adaptive_start`` = the
         iterations done (a multiple of ``every``).  LDS-resident float32 path only; not together with ``param_schedule``;
-        with ``check_stop`` it needs ``admm_convergence='per_sample'``.  For this call only."""
+        with ``check_stop`` it needs ``admm_convergence='per_sample'``.  For this call only.
+
+        ``band_params``: per-sample temporal band weights of a line-graph instance -- ``{'skip': [s_0 ... s_{B-1}]}``, integers
+        in ``[1, self.skip_connection]``: sample b solves on the line graph of skip-connection interval s_b (the table of
+        ``utils.skip_connection_tables``, zero beyond the interval, in the instance's width) and equals the B = 1 solve of an
+        instance constructed with ``skip_connection=s_b``, bit for bit.  ``band_sets`` / ``band_of_sample``: the low-level form
+        -- a list of ``(T, skip_connection)`` tables (row t = the weights of x[t-1-s]; arbitrary hop weights) and the index of
+        every sample's table.  For this call only.  Both paths, float32 and float64; on the LDS-resident path together with
+        ``sample_params``, the per-sample ``param_schedule``, ``adaptive_rho`` and per-sample stopping if wanted, on the
+        streaming path a fixed iteration count.  With ``check_stop`` it needs ``admm_convergence='per_sample'``.  The operator
+        methods (``apply_op_Ldr`` ...), ``CG_solver`` and ``two_loops`` keep reading the instance's own ``d_ew``."""
         args = parse_solve_args(self, y.shape[0], sample_params, graph_sets, graph_of_sample, graph_params, param_schedule,
-                                schedule_start, adaptive_rho, adaptive_start)
+                                schedule_start, adaptive_rho, adaptive_start, band_params, band_sets, band_of_sample)
         self.rho_history = self.rho_final = None
         dt, yd, md, mask_f32, (B, N, Cn) = self._stage_input(y, mask, differential)
         h, p = self._solver(Cn, dt, B)
@@ -605,14 +617,15 @@ class ADMM_algorithm():
             self.rho_final = np.ascontiguousarray(hist[last, :, np.arange(B)].T)
 
     def combined_loop(self, y, mask=None, differential=False, print_info=True, sample_params=None, param_schedule=None,
-                      adaptive_rho=None, **graph_kw):
+                      adaptive_rho=None, **graph_kw):          # (graph_kw: the graph and the band arguments)
         """``y`` (B, t_in, N, C) [or (B, T, N, C) with ``mask``] -> ``x`` (B, T, N, C), dtype/device of y.
         History attributes are filled like the reference's (ADMM.py:612-643).  ``sample_params``, ``param_schedule`` and the
-        graph arguments (``graph_params``, ``graph_sets``, ``graph_of_sample``) and ``adaptive_rho``: see ``solve``."""
+        graph arguments (``graph_params``, ``graph_sets``, ``graph_of_sample``), ``adaptive_rho`` and the band arguments
+        (``band_params``, ``band_sets``, ``band_of_sample``): see ``solve``."""
         return self.solve(y, mask=mask, differential=differential, print_info=print_info, return_state=False,
                           sample_params=sample_params, param_schedule=param_schedule, adaptive_rho=adaptive_rho, **graph_kw)[0]
 
-    def sweep(self, y, grid, mask=None, chunk=None, schedules=None, **solve_kw):
+    def sweep(self, y, grid, mask=None, chunk=None, schedules=None, skips=None, **solve_kw):
         """A grid search over ADMM weights and graph sigmas as one batch (the reference's notebooks run one ``combined_loop``
         per value).  ``y``: W windows; ``grid``: dict name -> list of values, the names out of the six ADMM weights and
         ``u_sigma`` / ``d_sigma`` (``solve(graph_params=...)``: one graph per distinct pair, the instance's neighbour lists).  The Cartesian product of the lists (P sets, in
@@ -626,7 +639,13 @@ class ADMM_algorithm():
         ``schedules``: dict name -> list of candidate schedules of that weight (1-D arrays of one length K, e.g.
         ``geometric_ramp``), crossed with ``grid`` after the grid's keys, in the same product order; a set then carries the
         candidate array under its name, and cell (p, w) runs ``solve(param_schedule=...)`` with column p * W + w holding the
-        candidates of set p (a comparison of ramps as one batch)."""
+        candidates of set p (a comparison of ramps as one batch).
+
+        ``skips``: skip-connection intervals of a line-graph instance (integers in ``[1, self.skip_connection]``), crossed with
+        ``grid`` after its keys and after ``schedules``, in the same product order; a set then carries ``'skip'``, and cell
+        (p, w) runs ``solve(band_params=...)`` with the interval of set p: it equals the B = 1 solve by an instance constructed
+        with ``skip_connection=sets[p]['skip']``."""
+        skip_vals = check_skips(self, skips) if skips is not None else None
         sched_names = list(schedules) if schedules else []
         for nm in sched_names:
             if nm not in SAMPLE_PARAM_NAMES:
@@ -642,8 +661,10 @@ class ADMM_algorithm():
         for nm in names:
             if nm not in SAMPLE_PARAM_NAMES + GRAPH_PARAM_NAMES:
                 raise ValueError(f"sweep: unknown key {nm!r} (expected some of {SAMPLE_PARAM_NAMES + GRAPH_PARAM_NAMES})")
-        sets = [dict(zip(names + sched_names, vals))
-                for vals in itertools.product(*([list(grid[nm]) for nm in names] + [cands[nm] for nm in sched_names]))]
+        skip_name = ["skip"] if skip_vals is not None else []
+        sets = [dict(zip(names + sched_names + skip_name, vals))
+                for vals in itertools.product(*([list(grid[nm]) for nm in names] + [cands[nm] for nm in sched_names]
+                                                + [skip_vals] * len(skip_name)))]
         W, P = y.shape[0], len(sets)
         total = P * W
         step = total if chunk is None else int(chunk)
@@ -659,6 +680,8 @@ class ADMM_algorithm():
             kw = dict(solve_kw, graph_params=gp) if gp else solve_kw
             if sched_names:          # column j of a (K, B) schedule: the candidate of sample j's set
                 kw = dict(kw, param_schedule={nm: np.stack([sets[j // W][nm] for j in s], axis=1) for nm in sched_names})
+            if skip_name:
+                kw = dict(kw, band_params={"skip": [sets[j // W]["skip"] for j in s]})
             xs.append(self.solve(y[w], mask=None if mask is None else mask[w], sample_params=sp, **kw)[0])
             ns.append(np.array(self.n_iters_per_sample, dtype=np.int32))
         x = torch.cat(xs, 0)

@@ -107,6 +107,7 @@ SYMBOLS = {
     "mgadmm_solver_set_param_schedule": (C.c_int, [_vp, C.POINTER(SampleParams), C.c_int32, C.c_int32, C.c_int32]),
     "mgadmm_solver_set_adaptive_rho": (C.c_int, [_vp, C.POINTER(AdaptiveRho), C.c_int32]),
     "mgadmm_solver_get_adaptive_history": (C.c_int, [_vp, C.c_int32, _f64p, C.c_int32, _i32p]),
+    "mgadmm_solver_set_sample_bands": (C.c_int, [_vp, C.c_int32, _f32p, _i32p, C.c_int32]),
     "mgadmm_solver_workspace_bytes": (C.c_int64, [_vp]),
     "mgadmm_solver_path": (C.c_int, [_vp, C.c_int32]),
     "mgadmm_solver_query": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int64)]),

@@ -1,5 +1,6 @@
 """What a solve is given beyond ``y`` and ``mask`` -- ``sample_params``, ``graph_params`` / ``graph_sets`` / ``graph_of_sample``,
-``param_schedule`` / ``schedule_start``, ``adaptive_rho`` / ``adaptive_start`` -- checked before the library is touched, and
+``param_schedule`` / ``schedule_start``, ``adaptive_rho`` / ``adaptive_start``, ``band_params`` / ``band_sets`` /
+``band_of_sample`` (their checks: ``band_args.py``) -- checked before the library is touched, and
 set on a solver for the solves of one ``with`` block.  No GPU work here; ``ADMM.py`` is the caller.
 
 Order of refusals, a contract like the one of ``csrc/solve_gate.h``: ``parse_solve_args`` raises the first that is due of
@@ -9,11 +10,12 @@ Order of refusals, a contract like the one of ``csrc/solve_gate.h``: ``parse_sol
   3. the graph arguments: ``graph_of_sample`` without sets, ``graph_params`` with ``graph_sets``, a line graph, then
      ``graph_params`` (which builds the tables of every distinct pair here) or ``graph_sets`` and ``graph_of_sample``;
   4. ``adaptive_rho`` and ``adaptive_start``;
-  5. ``adaptive_rho`` together with ``param_schedule``.
+  5. ``adaptive_rho`` together with ``param_schedule``;
+  6. the band arguments (``band_args.check_band_args``).
 ``y`` and ``mask`` are checked after all of these, ``warm_start`` inside the scope, after the set calls.
 
 Order of set and clear calls: ``solve_scope`` sets the sample table, the graph table (its device graphs created first), the
-schedule and the adaptive penalties, and clears them in the reverse order with the return codes ignored.  A set call that
+schedule, the adaptive penalties and the band table, and clears them in the reverse order with the return codes ignored.  A set call that
 refuses raises ``MgadmmError`` and is not cleared, what was set before it is; the graph table alone is cleared whenever it
 was entered -- also when a graph could not be created or its set call refused -- and its graphs are closed after that.
 """
@@ -25,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .band_args import check_band_args
 
 SAMPLE_PARAM_NAMES = ("rho", "rho_u", "rho_d", "mu_u", "mu_d1", "mu_d2")
 GRAPH_PARAM_NAMES = ("u_sigma", "d_sigma")
@@ -206,11 +209,11 @@ def _check_graph_sets(blk, graph_sets, graph_of_sample, graph_params, B):
 
 
 # the checked arguments of one call: the outputs of the four checkers (None where the argument was not given) and the start values
-SolveArgs = collections.namedtuple("SolveArgs", "sp sch gs ar schedule_start adaptive_start")
+SolveArgs = collections.namedtuple("SolveArgs", "sp sch gs ar schedule_start adaptive_start bs", defaults=(None,))
 
 
 def parse_solve_args(blk, B, sample_params=None, graph_sets=None, graph_of_sample=None, graph_params=None, param_schedule=None,
-                     schedule_start=0, adaptive_rho=None, adaptive_start=0):
+                     schedule_start=0, adaptive_rho=None, adaptive_start=0, band_params=None, band_sets=None, band_of_sample=None):
     """``solve``'s keywords for a batch of B samples of the instance ``blk`` as ``SolveArgs``, in the module's order of refusals."""
     sp = _check_sample_params(sample_params, B) if sample_params is not None else None
     sch = _check_param_schedule(param_schedule, B, schedule_start, sp) if param_schedule is not None else None
@@ -218,7 +221,8 @@ def parse_solve_args(blk, B, sample_params=None, graph_sets=None, graph_of_sampl
     ar = _check_adaptive_rho(adaptive_rho, adaptive_start) if adaptive_rho is not None else None
     if ar is not None and sch is not None:
         raise ValueError("adaptive_rho and param_schedule exclude each other (the adaptation writes the table a schedule would fill)")
-    return SolveArgs(sp, sch, gs, ar, schedule_start, adaptive_start)
+    bs = check_band_args(blk, band_params, band_sets, band_of_sample, B)
+    return SolveArgs(sp, sch, gs, ar, schedule_start, adaptive_start, bs)
 
 
 @contextlib.contextmanager
@@ -272,4 +276,9 @@ def solve_scope(blk, h, Cn, B, args):
                                         (h, C.byref(_table(arrays)), n_rows, cols, int(args.schedule_start)), (h, None, 0, 0, 0)))
         if args.ar is not None:
             scope.enter_context(_scoped(lib.mgadmm_solver_set_adaptive_rho, (h, C.byref(args.ar[0]), int(args.adaptive_start)), (h, None, 0)))
+        if args.bs is not None:
+            tables, bos = args.bs
+            scope.enter_context(_scoped(lib.mgadmm_solver_set_sample_bands,
+                                        (h, len(tables), tables.ctypes.data_as(C.POINTER(C.c_float)), bos.ctypes.data_as(C.POINTER(C.c_int32)), B),
+                                        (h, 0, None, None, 0)))
         yield
