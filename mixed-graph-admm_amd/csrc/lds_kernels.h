@@ -159,6 +159,14 @@ __device__ __forceinline__ void stg(float* base, unsigned boff, float v) {
 }
 // REQUEST fence: the loads before it are issued together and waited for together, nothing crosses it.
 #define MG_REQ_FENCE() asm volatile("" ::: "memory")
+// the constant address space, as a qualifier of the pointee: a workgroup-uniform read through such a pointer is a scalar load
+// (the kernarg segment, and tables that do not change while a launch runs).  The host pass of the single-source compile
+// has no address spaces and reads through the plain pointer.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MG_CONST_AS __attribute__((address_space(4)))
+#else
+#define MG_CONST_AS
+#endif
 // a workgroup-uniform value the optimiser must keep in a scalar register from here on (it would otherwise re-read a launch
 // argument from the kernarg segment inside a CG loop: a scalar load shares its counter with the LDS gathers in flight)
 #define MG_PIN_S(x) asm volatile("" : "+s"(x))
@@ -861,21 +869,24 @@ __device__ __forceinline__ int lds_cg(LdsCtx<TPG, BAND, NU, ND, TP>& c, BlockRed
 // (a scalar load, so the values stay in scalar registers as the arguments did; the table does not change while a launch
 // runs).  The same arithmetic in the same order otherwise.  The stop test of PS is compiled into these kernels too and runs
 // when the launch carries stop words (MG_LDS_PSTOP_ON): a sweep runs a fixed count or stops per sample.  Again a flag of the
-// translation unit: the kernels k_admm_lds_pp of lds_launch_pp.hip; in the other two units both macros expand to what the
-// source said before them.
+// translation unit: the kernels k_admm_lds_pp of lds_launch_pp.hip.
+// The switches of a unit, all set in the block below and nowhere else (the PP unit | the other two):
+//   MG_LDS_KERNEL          the kernels' name: k_admm_lds_pp | k_admm_lds_ps, k_admm_lds
+//   MG_LDS_PS              the per-sample stop test is compiled in: true | true in the PS unit, false in the default one
+//   MG_LDS_PSTOP_ON(args)  ... and runs: when the launch carries stop words | always
+//   MG_LDS_W(field)        a weight of this trip: field of the trip's record of LdsArgs::sp | the kernel argument a.field
+//   MG_LDS_W_NEXT(f, now)  a weight of the next trip: field f of its record | `now`
+//   MG_LDS_WREC_DECL       at the head of the trip body: the number of the trip's record, a pinned scalar | nothing
+//   MG_LDS_IMG(args)       base of the graph image: the image of the workgroup's weight set | args.csr
+//   MG_LDS_BAND_OF_SAMPLE  before the trip's first operator: LdsCtx::band_w of the workgroup's band set | nothing
+// In the other two units every one of them expands to what the source said before the switch existed.
 #ifdef MGADMM_LDS_PER_SAMPLE_PARAMS
 #define MG_LDS_KERNEL k_admm_lds_pp
 #define MG_LDS_PS true
 #define MG_LDS_PSTOP_ON(args) ((args).pstop != nullptr)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MG_LDS_W(field) (((const LdsSampleParams __attribute__((address_space(4)))*)a.sp)[wrec].field)
-#define MG_LDS_W_NEXT(field, now) (((const LdsSampleParams __attribute__((address_space(4)))*)a.sp)[MG_LDS_WREC_OF(trip + 1)].field)
+#define MG_LDS_W(field) (((const LdsSampleParams MG_CONST_AS*)a.sp)[wrec].field)
+#define MG_LDS_W_NEXT(field, now) (((const LdsSampleParams MG_CONST_AS*)a.sp)[MG_LDS_WREC_OF(trip + 1)].field)
 #define MG_LDS_WREC_DECL unsigned wrec = MG_LDS_WREC_OF(trip); MG_PIN_S(wrec)
-#else
-#define MG_LDS_W(field) (a.sp[wrec].field)
-#define MG_LDS_W_NEXT(field, now) (a.sp[MG_LDS_WREC_OF(trip + 1)].field)
-#define MG_LDS_WREC_DECL const unsigned wrec = MG_LDS_WREC_OF(trip)
-#endif
 // Per-iteration weights (mgadmm_solver_set_param_schedule): the table holds sp_rows rows of records at a stride of sp_stride
 // records, and the trip reads the row of ITS iteration, sched_row (lds_param_table.h) of the launch's first iteration + trip:
 // kernel arguments, the trip counter and the workgroup number only, so the record number is a scalar value formed once per
@@ -891,12 +902,23 @@ __device__ __forceinline__ int lds_cg(LdsCtx<TPG, BAND, NU, ND, TP>& c, BlockRed
 // where it is used, from a workgroup-uniform load of the set number through the constant address space like MG_LDS_W: it
 // stays a scalar register pair, and every read of weights (the copy to LDS, the register rows, the diagonals) goes through
 // it.  node_of_row and the offsets in the entries are structure, equal in every set.
-#if defined(__HIP_DEVICE_COMPILE__)
 #define MG_LDS_IMG(args) ((args).csr + ((args).gset != nullptr ? (size_t)(unsigned)(args).img_stride * \
-                          (size_t)(unsigned)((const int __attribute__((address_space(4)))*)(args).gset)[b] : (size_t)0))
-#else
-#define MG_LDS_IMG(args) ((args).csr + ((args).gset != nullptr ? (size_t)(args).img_stride * (size_t)(args).gset[b] : (size_t)0))
-#endif
+                          (size_t)(unsigned)((const int MG_CONST_AS*)(args).gset)[b] : (size_t)0))
+// Per-sample temporal band weights (mgadmm_solver_set_sample_bands, band_sets.h): LdsArgs::band_w holds the tables of S sets
+// back to back, T * skip floats each, and workgroup b of a BAND instance reads the one of set bset[b] (no table: the graph's
+// own).  The trip body sets LdsCtx::band_w from the launch arguments; MG_LDS_BAND_OF_SAMPLE then, once per trip and before
+// any operator runs, moves it to the set's table: one workgroup-uniform base from a scalar load of the set number, as
+// MG_LDS_IMG forms the image base.  band_back / band_fwd read through LdsCtx::band_w either way.  Instances without BAND never
+// read band_w: the first overload, empty.
+template <class Ctx, class Args>
+__device__ __forceinline__ void mg_lds_band_of_sample(Ctx&, Args, int) {}
+template <int TPG, int NU, int ND, int TP, class Args>
+__device__ __forceinline__ void mg_lds_band_of_sample(LdsCtx<TPG, true, NU, ND, TP>& c, Args a, int b) {
+    if (a->bset == nullptr) return;
+    const unsigned set = (unsigned)((const int MG_CONST_AS*)a->bset)[b];
+    c.band_w = a->band_w + (size_t)(unsigned)(a->T * a->skip) * (size_t)set;
+}
+#define MG_LDS_BAND_OF_SAMPLE(c, kp, b) mg_lds_band_of_sample(c, kp, b)
 #else
 #ifdef MGADMM_LDS_PER_SAMPLE_STOP
 #define MG_LDS_KERNEL k_admm_lds_ps
@@ -910,6 +932,7 @@ __device__ __forceinline__ int lds_cg(LdsCtx<TPG, BAND, NU, ND, TP>& c, BlockRed
 #define MG_LDS_W_NEXT(field, now) (now)
 #define MG_LDS_WREC_DECL do { } while (0)
 #define MG_LDS_IMG(args) (args).csr
+#define MG_LDS_BAND_OF_SAMPLE(c, kp, b) do { } while (0)
 #endif
 template <int TPG, bool BAND, int MAXT, bool SB, int NU = 0, int ND = 0, bool SLOTS = false, int TP = -1>
 __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERNEL(LdsArgs a_in) {
@@ -974,11 +997,11 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
     // alive across the three solves (92 spilled SGPRs, 118 spilled VGPRs in round 3's first attempt).  So every trip re-reads
     // its arguments from the kernarg segment through a copy of the segment pointer the optimiser cannot see through, and
     // re-derives its indices from opaque copies of the thread and workgroup number.
+    typedef const LdsArgs MG_CONST_AS* KernargPtr;                            // the kernarg segment: constant address space, scalar loads
 #if defined(__HIP_DEVICE_COMPILE__)
-    typedef const LdsArgs __attribute__((address_space(4))) * KernargPtr;     // the kernarg segment: constant address space, scalar loads
     KernargPtr kp = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();       // LdsArgs is the kernel's only argument: offset 0
 #else
-    const LdsArgs* kp = &a_in;                                                  // (host pass of the single-source compile)
+    KernargPtr kp = &a_in;                                                    // (host pass of the single-source compile)
 #endif
     const int J = a_in.J;
     float xc[TPG], vc[TPG];          // carried from trip to trip: the iterate and gamma + rho phi
@@ -989,10 +1012,8 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
     asm volatile("" : "+s"(kp));
     asm volatile("" : "+v"(tid));
     asm volatile("" : "+s"(b));
-    const LdsArgs __attribute__((address_space(4)))& a = *kp;
-#else
-    const LdsArgs& a = *kp;
 #endif
+    const LdsArgs MG_CONST_AS& a = *kp;
     const bool first = a.first && trip == 0;      // phi = Ldr x0 is formed by the first trip of a cold start
     // diagnostic build (make EXTRA=-DMGADMM_PHASE_CLOCK): the per-sample metric slots receive the 100 MHz clock at the phase
     // boundaries of the trip instead of the metrics (tools/lds_phase_clock.py)
@@ -1072,6 +1093,7 @@ __global__ __launch_bounds__(MAXT, (SB && MAXT == 640) ? 5 : 1) void MG_LDS_KERN
         }
     };
     if (first) fetch_d();
+    MG_LDS_BAND_OF_SAMPLE(c, kp, b);
     fetch_t();
     const size_t sb = (size_t)b * a.TN;
     const float* xo = kp->xs[trip] + sb;          // iteration k reads xs[k] and writes xs[k+1]

@@ -7,7 +7,9 @@ mgadmm_solver_set_sample_bands): sample b of a batch on a line-graph instance of
     at +0 bit for bit;
   * streaming path (float32 and float64): the geometry depends on B, so the twin is the whole batch solved on an instance of
     set s; every sample of the table solve whose set is s equals that solve's sample bit for bit;
-  * both against the float64 oracle run per sample with the sample's table, at the project's tolerances.
+  * both against the float64 oracle run per sample with the sample's table, at the project's tolerances;
+  * every BAND instance of k_admm_lds_pp (the ten band rows of tests/lds_census.py, widths 1 and 3): three samples of one
+    window under the graph's own table times 1, 0.5 and 0.25 against B = 1 solves of instances carrying that table, bit for bit.
 
 The problem (tests/band_sets_cases.py) is the smallest on which each kernel can go wrong; every test asserts that two samples
 of one window under different sets differ by more than 100 x its tolerance, so a kernel that ignores the table cannot pass."""
@@ -21,7 +23,7 @@ import band_sets_cases as bc
 import lds_census as lc
 from conftest import admm_info_from
 from helpers import check_windows
-from test_gpu_lds_census import env  # noqa: F401
+from test_gpu_lds_census import _info, _inputs, _product, env  # noqa: F401
 from test_gpu_sample_params import _solve
 
 pytestmark = pytest.mark.gpu
@@ -344,3 +346,52 @@ def test_sweep_over_skip_connection_intervals():
             assert torch.equal(x[p, w], one.solve(y[w:w + 1])[0][0]), (p, w)
         one.close()
     blk.close()
+
+
+# ---------------------------------------------------------------------------------------------------------- 8
+BAND_ROWS = [r for r in lc.CENSUS if r["expect"].split(", ")[1] == "true"]      # the ten BAND instances
+ROW_FACTORS = (1.0, 0.5, 0.25)          # the graph's own table times a power of two: exact in float32 at width 1 and width 3
+ROW_SET_OF_SAMPLE = [2, 0, 1]
+ROW_IT = 3
+
+
+@pytest.mark.parametrize("r", BAND_ROWS, ids=lc.row_id)
+def test_every_band_instance_reads_the_table_of_its_sample(r, env):
+    """Every BAND instance of k_admm_lds_pp (the census row's problem, with the zd solve on so the trip reads the temporal rows
+    twice): ONE window three times in a batch, sample b under the graph's own band table times ROW_FACTORS[ROW_SET_OF_SAMPLE[b]],
+    three iterations.  The launch reports unit 2 and the row's instance; every sample equals, bit for bit, the B = 1 solve of
+    an instance whose d_ew is overwritten with its set (k_admm_lds, unit 0); the three solutions, which differ by nothing
+    but the table, lie more than 100 x the float32 tolerance apart."""
+    from mgadmm import _lib
+    assert len(BAND_ROWS) == 10
+    for k, v in r["env"].items():
+        env.setenv(k, v)
+    B, abl = len(ROW_SET_OF_SAMPLE), "None" if r["abl"] == "DGLR" else r["abl"]          # 'DGLR' has no zd solve
+    r = dict(r, abl=abl, B=1)
+    info = _info(r["N"], r["T"])
+    y1, m1 = _inputs(r)
+    y = torch.from_numpy(y1).repeat(B, 1, 1, 1)
+    mask = None if m1 is None else torch.from_numpy(m1).repeat(B, 1, 1, 1)
+    tag = f"{r['expect']} N={r['N']} T={r['T']} {r['kind']} {abl} {r['task']}"
+
+    blk = _prep(_product(r, info, path="lds"), ROW_IT)
+    own = blk.d_ew[:, :, 0].numpy().copy()                                               # (T, skip) float32
+    sets = [own * np.float32(f) for f in ROW_FACTORS]
+    batch = _solve(blk, y, abl, mask=mask, band_sets=sets, band_of_sample=np.array(ROW_SET_OF_SAMPLE, dtype=np.int32))
+    assert _path(blk, B) == _lib.PATH_LDS and _unit(blk) == 2, tag
+    assert _lib.lds_instance(_handle(blk)) == r["expect"], (tag, _lib.lds_instance(_handle(blk)))
+    assert batch["n_iters"] == ROW_IT and (batch["n"] == ROW_IT).all(), tag
+    blk.close()
+
+    for b, j in enumerate(ROW_SET_OF_SAMPLE):
+        t = _prep(_product(r, info, path="lds"), ROW_IT)
+        t.d_ew = torch.from_numpy(sets[j])[:, :, None].repeat(1, 1, r["N"])
+        one = _solve(t, y[b:b + 1], abl, mask=None if mask is None else mask[b:b + 1])
+        assert _unit(t) == 0 and _lib.lds_instance(_handle(t)) == r["expect"], (tag, b)
+        _assert_sample_equals(batch, b, one, 0, tag)
+        t.close()
+
+    x = batch["x"].double()
+    apart = [float((x[a] - x[b]).norm() / x[b].norm()) for a, b in ((0, 1), (0, 2), (1, 2))]
+    print(f"\n[band rows] {tag}: the three sets apart by {apart}")
+    assert min(apart) > 100 * bc.F32_TOL["xtol"], (tag, apart)

@@ -6,7 +6,7 @@ it needs a GPU.
     written out there; the refusals by name; a rule that never steps leaving fill_records of the start weights;
   * the rule restated in numpy (tests/adaptive_rho_cases.py) against the program on 10^4 random inputs, exactly;
   * the header's declarations, the version line, the ctypes mirror, the exported symbols;
-  * lds_schedule.h and lds_kernels.h are what they were before the feature;
+  * lds_schedule.h is what it was before the feature, and the kernels of lds_kernels.h compile to the recorded instructions;
   * validation in Python before the library is touched;
   * the float64 twin: every decision at least 1 % from its threshold, steps in both directions, and a solution that differs
     from the constant-penalty one by >= 1e-2 per sample, so a kernel that ignores the table cannot pass a 1e-5 comparison."""
@@ -118,11 +118,28 @@ def test_the_headers_are_plain_cxx():
     assert "/" not in body and "+" not in body and "fma" not in body         # multiplications, comparisons, selects
 
 
-def test_the_kernels_and_the_schedule_are_untouched():
-    want = {"lds_schedule.h": "9b432bec77744dd2aa1fcde80ec11a8859a8c98b899b76242606e772e6866f5e",
-            "lds_kernels.h": "30e7cb1fec55bc1aa6bbe6be644f70e49b4ae481987de966c77021476b7011d1"}
-    for name, sha in want.items():
-        assert hashlib.sha256(open(os.path.join(PKG, "csrc", name), "rb").read()).hexdigest() == sha, name
+@pytest.fixture(scope="module")
+def kernel_isa():
+    """tools/kernel_isa.py and the manifest of the tree under test: the three LDS units compiled once, side by side."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_isa as ki
+    golden = json.load(open(ki.GOLDEN))
+    if ki.hipcc_version() != golden["hipcc"]:
+        pytest.skip(f"the recorded kernels are those of '{golden['hipcc']}'; this compiler is '{ki.hipcc_version()}'")
+    return ki, golden, ki.manifest(ROOT)
+
+
+def test_the_kernels_and_the_schedule_are_untouched(kernel_isa):
+    """lds_schedule.h byte for byte; every k_admm_lds / k_admm_lds_ps / k_admm_lds_pp instance compiles to the instructions,
+    registers, spills and scratch recorded in tests/golden/lds_kernel_isa.json (a change that means to move a kernel
+    regenerates the file with `python tools/kernel_isa.py`, and the diff names the kernels that moved)."""
+    sha = "9b432bec77744dd2aa1fcde80ec11a8859a8c98b899b76242606e772e6866f5e"
+    assert hashlib.sha256(open(os.path.join(PKG, "csrc", "lds_schedule.h"), "rb").read()).hexdigest() == sha, "lds_schedule.h"
+    ki, golden, here = kernel_isa
+    assert len(golden["kernels"]) == len(here["kernels"]) == 135
+    assert {r["unit"] for r in golden["kernels"]} == set(ki.LDS_UNITS)
+    moved = ki.difference(golden, here)
+    assert here["kernels"] == golden["kernels"] and not moved, "\n" + "\n".join(moved)
 
 
 # ------------------------------------------------------------------------------------------------ ABI
