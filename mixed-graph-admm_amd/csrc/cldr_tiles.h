@@ -18,7 +18,7 @@ struct CldrCaps {
     int GD, GT;               // entry slots per W_d row and per W_d^T row
 };
 
-// Tile geometries of k_cldr by number (MGADMM_CLDR_GEOM; engine.h, ClG1 ... ClG4): VECT columns per lane, NW waves, rows per
+// Tile geometries of k_cldr by number (MGADMM_CLDR_GEOM; stream_plan.h picks one, engine.h has them as ClG1 ... ClG4): VECT columns per lane, NW waves, rows per
 // wave of the tile (MA) / of C1 (MQ) / of C2 (MP).  The caps of a geometry are NW * MA, NW * MQ, NW * MP rows.
 struct CldrGeomDims { int VECT, NW, MA, MQ, MP; };
 constexpr CldrGeomDims CLDR_GEOMS[5] = {

@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <tuple>
 #include <type_traits>
 
 #include "common.h"
@@ -17,6 +18,7 @@
 #include "tile_meta.h"
 #include "stream_keys.h"
 #include "stream_kernels.h"
+#include "stream_plan.h"
 #include "lds_adapt.h"      // ldsadapt::Params, validate: set_adaptive_rho checks its arguments for either scalar type
 #include "lds_plan.h"
 #include "lds_param_table.h"
@@ -61,23 +63,18 @@ struct Engine : EngineBase {
     double* h_row = nullptr;
     int* h_flag = nullptr;
     hipEvent_t ev_ring[LAG + 1] = {nullptr};
-    int want_blocks = 2048;
     struct TileMetaDev { int R = 0; int GW = 0; int* tl_col = nullptr; float* tl_w = nullptr; int* halo = nullptr; int* h_rowptr = nullptr; int* h_col = nullptr; float* h_val = nullptr; };
     TileMetaDev tmeta[3];         // W_u, W_d, W_d^T metadata for the tile size in use
     // fused cLdr kernel (k_cldr): tile tables for the geometry in use; state 0 = not built yet, 1 = usable, -1 = the graph
     // does not fit its slot counts (hub rows): the two-pass form stays
     struct CldrDev {
         int state = 0, NT = 0;
+        int gd = 8, gt = 12;      // W_d / W_d^T slots per row of the tables (streamplan::cldr_slots)
         int *n0 = nullptr, *nC = nullptr, *rows = nullptr, *dcol = nullptr, *dcnt = nullptr, *tcol = nullptr, *tcnt = nullptr;
         float *dw = nullptr, *tw = nullptr;
     } cldr_dev;
-    int use_fused = 1;            // MGADMM_FUSED=0 keeps the two-pass cLdr (tests compare the two)
-    int use_fold = 1;             // MGADMM_FOLD=0: p = r + beta p and x += alpha p stay in their own kernel (EpiPUpdate)
-    int use_fold_lu = 1;          // MGADMM_FOLD_LU=0: the same for the Lu kernel of the zu solve only
-    int sweep_rev = 1;            // MGADMM_SWEEP_REV=0: r -= alpha Ap sweeps the time slices upwards like every other kernel
-    int cldr_tile_major = 1;      // MGADMM_CLDR_ORDER=0: chunks of a tile adjacent in dispatch order
+    streamplan::Planner plan;     // geometry and kernel choice of the streaming path (stream_plan.h); its switches are read in init_workspace
     int cur_P = 0;                // partial rows written by the last row-kernel launch (k_rows or k_tile)
-    int use_tile = 1;             // LDS-tiled spatial kernel on cluster-ordered graphs (reorder = 2); MGADMM_TILE=0 disables
     int64_t ws_bytes = 0;
     // LDS-resident fused path (float32, small graphs): the plan record (none for float64), what the queries report of its last
     // launch, and the host state of the per-sample features solve_gate.h decides on.  The device side: LdsEngine (lds_engine.h)
@@ -99,7 +96,6 @@ struct Engine : EngineBase {
     int bs_Bp = 0;
     const float* band_wb = nullptr;
     StreamKeyLog stream_keys;        // MGADMM_Q_STREAM_KEYS / _KEY0 + i: distinct k_rows / k_tile / k_cldr instances launched (stream_keys.h)
-    static constexpr bool IS_F64 = std::is_same<S, double>::value;
     // profiling
     bool prof_on = false;
     std::vector<hipEvent_t> prof_ev;
@@ -132,55 +128,17 @@ struct Engine : EngineBase {
         for (auto& e : prof_ev) (void)hipEventDestroy(e);
     }
 
-    // ---------------------------------------------------------------- geometry
-    Geom make_geom(int B) const {
-        Geom q;
-        q.T = T; q.N = N; q.B = B;
-        int vecw;
-        if (sizeof(S) == 4) vecw = B >= 192 ? 4 : (B >= 96 ? 2 : 1);
-        else vecw = B >= 96 ? 2 : 1;
-        const int cw = 64 * vecw;
-        q.VEC = vecw;
-        q.Bp = (B + cw - 1) / cw * cw;
-        q.CH = q.Bp / cw;
-        // persistent-sized grid: ~want_blocks workgroups in total, a multiple of 8 per column chunk
-        int g8 = want_blocks / (8 * q.CH);
-        if (g8 < 1) g8 = 1;
-        q.G8 = g8;
-        q.P = 8 * g8;
-        // rows per work item: 16 (4 per wave) unless the problem is too small to give every workgroup two items
-        long rows = (long)T * N;
-        int ri = 16;
-        while (ri > 4 && rows / ri < 2L * q.P) ri -= 4;
-        q.RI = ri;
-        const int per_xcd = (N + 7) / 8;
-        q.NBL = (per_xcd + ri - 1) / ri;
-        q.NX = q.NBL * ri;
-        q.n_items = T * q.NBL;
-        q.grid = q.P * q.CH;
-        q.rev = 0;
-        return q;
+    // ---------------------------------------------------------------- geometry (the rules: stream_plan.h)
+    streamplan::Facts plan_facts() const {
+        streamplan::Facts f;
+        f.elem = (int)sizeof(S); f.T = T; f.N = N; f.spatial = g->mode == MGADMM_TEMPORAL_SPATIAL; f.reorder = g->reorder; f.q1 = g->q1;
+        f.max_u = g->Wu.max_row; f.max_d = g->Wd.max_row; f.max_dt = g->WdT.max_row; f.avg_dt = g->WdT.avg_row_ceil;
+        return f;
     }
-
-    // geometry of the LDS-tiled spatial kernel for the same column layout as `q`
-    bool make_tile_geom(const Geom& q, TileGeom& tg) const {
-        if (!use_tile || g->reorder < 2 || g->mode != MGADMM_TEMPORAL_SPATIAL) return false;
-        tg.T = T; tg.N = N; tg.B = q.B; tg.Bp = q.Bp; tg.VEC = q.VEC; tg.CH = q.CH;
-        // tile size: 8 rows (2 per wave).  With the rows per wave a template constant the register footprint
-        // follows the tile size (EpiLhs: 100 VGPRs at 2 rows, 148 at 5), and the kernel is latency-bound, so
-        // more resident workgroups win: SpMM inside CG on the 10k-node graph 4.30 TB/s at 20 rows, 4.60 at 12,
-        // 4.72 at 8, 4.71 at 4 (more halo reads); the 100k-node graph is flat (4.86 -> 4.91).  MGADMM_TILE_R=20
-        // selects the large tile for experiments.
-        int best = 8;
-        if (const char* e = getenv("MGADMM_TILE_R")) { int rr = atoi(e); if (rr == 8 || rr == 20) best = rr; }
-        tg.R = best;
-        tg.NTILE = (N + best - 1) / best;
-        tg.TPX = (tg.NTILE + 7) / 8;
-        tg.P = 8 * tg.TPX;
-        tg.grid = tg.P * q.CH;
-        const size_t row_bytes = (size_t)64 * q.VEC * sizeof(S);
-        tg.lds_bytes = (int)std::max(row_bytes * (best + TILE_HMAX), (size_t)3 * q.VEC * 64 * sizeof(S));
-        return true;
+    // which matrix a spatial operator applies (the graph hands out its three device tables; transpose_by_gather: Ldr^T reads W_d's)
+    streamplan::Mat mat_of(const OpDesc& op) const {
+        if (op.kind != OPK_SPATIAL) return op.kind == OPK_BAND ? streamplan::M_BAND : streamplan::M_NONE;
+        return op.rowptr == g->Wu.rowptr ? streamplan::M_WU : (op.rowptr == g->Wd.rowptr ? streamplan::M_WD : streamplan::M_WDT);
     }
 
     // host-side preprocessing of one CSR matrix for tile size R (see TileMeta in stream_kernels.h)
@@ -196,7 +154,7 @@ struct Engine : EngineBase {
             const int ntile = tm.ntile;
             const std::vector<int>&tc = tm.tl_col, &hr = tm.h_rowptr, &hcol = tm.h_col, &halo = tm.halo;
             const std::vector<float>&tw = tm.tl_w, &hval = tm.h_val;
-            if (getenv("MGADMM_TILE_STATS")) {           // diagnostics: how well the tile geometry fits the graph
+            if (plan.sw.tile_stats) {           // diagnostics: how well the tile geometry fits the graph
                 long hsum = 0; int hfull = 0;
                 for (int tl = 0; tl < ntile; ++tl) {
                     int c = 0;
@@ -233,62 +191,34 @@ struct Engine : EngineBase {
 
     // ---------------------------------------------------------------- fused cLdr kernel (k_cldr)
     // Tile geometries (VECT columns per lane, NW waves, rows per wave of the tile / of C1 / of C2).  LDS per workgroup =
-    // NW * (MQ + MP) * 64 * VECT * sizeof(S).  MGADMM_CLDR_GEOM selects one (experiments); default per scalar type below.
+    // NW * (MQ + MP) * 64 * VECT * sizeof(S).  Which one is in force: streamplan::Planner (plan.geom), with the measurements.
     template <int VECT_, int NW_, int MA_, int MQ_, int MP_, int MINW_>
     struct ClG { static constexpr int VECT = VECT_, NW = NW_, MA = MA_, MQ = MQ_, MP = MP_, MINW = MINW_; };
-    // measured on cfg3 (N = 10 000, B = 512), SpMM + LHS launch / with the folded vector update:
-    //   geometry 1  380 us / 644 us      geometry 2  700 us / -      (a 16 / 32 / 48-row geometry 0 of 80 KiB ran 365 us / 711 us and
-    //   spilled 52 VGPRs in the folded form: removed in round 3)
     // (the numbers live in cldr_tiles.h, CLDR_GEOMS: the CPU replay of the tile builder reads the same table)
     template <int I, int MINW_>
     using ClGOf = ClG<CLDR_GEOMS[I].VECT, CLDR_GEOMS[I].NW, CLDR_GEOMS[I].MA, CLDR_GEOMS[I].MQ, CLDR_GEOMS[I].MP, MINW_>;
-    typedef ClGOf<1, 4> ClG1;     // 16 / 32 / 40 rows of 256 columns: 72 KiB (float), two workgroups per CU   (default)
-    typedef ClGOf<2, sizeof(S) == 4 ? 4 : 2> ClG2;   // 64 / 88 / 120 rows of 64 columns: 52 KiB (float) / 104 KiB (double); float: 128 VGPRs (6 waves per SIMD = 80 VGPRs spilled 87-100 of them in the folded form)
-    typedef ClGOf<3, 4> ClG3;    // 32 / 64 / 80 rows of 128 columns: 72 KiB (float): twice the rows per tile, a smaller halo share
-    typedef ClGOf<4, 4> ClG4;    // 32 / 48 / 64 rows of 256 columns, 16 waves: 112 KiB (float), one workgroup per CU
-    // W_d^T slots per row: 12, or 16 / 24 when a row is longer (round 3: the PEMS-like graphs of 600 ... 2000 nodes have rows of 13 and
-    // 14 entries and fell back to the two-pass path; the 16-slot instance is 5 % slower on graphs that do not need it).
-    // W_d slots: 6 (no test at all) when no row is longer, else 8
-    int cl_gt = 12;
-    int cl_gd = 8;
-    int cl_geom = sizeof(S) == 4 ? 1 : 2;   // float64: the narrow geometry (104 KiB)
-    void cl_dims(int& vect, int& nw, int& ma, int& mq, int& mp) const {
-        switch (cl_geom) {
-            case 1: vect = ClG1::VECT; nw = ClG1::NW; ma = ClG1::MA; mq = ClG1::MQ; mp = ClG1::MP; break;
-            case 3: vect = ClG3::VECT; nw = ClG3::NW; ma = ClG3::MA; mq = ClG3::MQ; mp = ClG3::MP; break;
-            case 4: vect = ClG4::VECT; nw = ClG4::NW; ma = ClG4::MA; mq = ClG4::MQ; mp = ClG4::MP; break;
-            default: vect = ClG2::VECT; nw = ClG2::NW; ma = ClG2::MA; mq = ClG2::MQ; mp = ClG2::MP; break;
-        }
-    }
-    bool cldr_usable() {
-        if (!use_fused || !use_tile || g->reorder < 2 || g->mode != MGADMM_TEMPORAL_SPATIAL) return false;
+    typedef ClGOf<1, streamplan::cldr_minw(1, sizeof(S))> ClG1;     // 16 / 32 / 40 rows of 256 columns: 72 KiB (float), two workgroups per CU   (default)
+    typedef ClGOf<2, streamplan::cldr_minw(2, sizeof(S))> ClG2;    // 64 / 88 / 120 rows of 64 columns: 52 KiB (float) / 104 KiB (double)
+    typedef ClGOf<3, streamplan::cldr_minw(3, sizeof(S))> ClG3;    // 32 / 64 / 80 rows of 128 columns: 72 KiB (float): twice the rows per tile, a smaller halo share
+    typedef ClGOf<4, streamplan::cldr_minw(4, sizeof(S))> ClG4;    // 32 / 48 / 64 rows of 256 columns, 16 waves: 112 KiB (float), one workgroup per CU
+    // tiles of the tables, built and uploaded at the first operator application; 0: no fused kernel for this solver
+    int cldr_tiles() {
+        if (!plan.cldr_wanted()) return 0;
         if (cldr_dev.state == 0) cldr_prepare();
-        return cldr_dev.state == 1;
+        return cldr_dev.state == 1 ? cldr_dev.NT : 0;
     }
     void cldr_prepare() {
         cldr_dev.state = -1;
-        if (const char* e = getenv("MGADMM_CLDR_GEOM")) { const int v = atoi(e); if (v >= 1 && v <= 4 && (v <= 2 || sizeof(S) == 4)) cl_geom = v; }
-        int vect, nw, ma, mq, mp;
-        cl_dims(vect, nw, ma, mq, mp);
-        if ((size_t)nw * (mq + mp) * 64 * vect * sizeof(S) > 150 * 1024) { cl_geom = 2; cl_dims(vect, nw, ma, mq, mp); }
         HostCsr A, At;
         if (g->has_perm) { mg_permute_csr(g->hWd, g->perm, g->iperm, A); mg_permute_csr(g->hWdT, g->perm, g->iperm, At); }
         else { A = g->hWd; At = g->hWdT; }
-        cl_gd = 6;
-        cl_gt = 12;
-        for (int i = 0; i < N; ++i) {
-            if (A.rowptr[i + 1] - A.rowptr[i] > 6) cl_gd = 8;
-            const int tl = At.rowptr[i + 1] - At.rowptr[i];
-            if (tl > 12) cl_gt = std::max(cl_gt, tl > 16 ? 24 : 16);
-        }
-        CldrCaps caps{nw * ma, nw * mq, nw * mp, cl_gd, cl_gt};
+        std::tie(cldr_dev.gd, cldr_dev.gt) = streamplan::cldr_slots(A, At);
+        const CldrCaps caps = cldr_caps_of(plan.geom, cldr_dev.gd, cldr_dev.gt);
         CldrTiles tl;
-        int row_limit = 0;
-        if (const char* e = getenv("MGADMM_CLDR_ROWS")) row_limit = atoi(e);
-        if (!build_cldr_tiles(A, At, g->cluster_starts, caps, tl, row_limit)) return;
-        if (getenv("MGADMM_TILE_STATS"))
+        if (!build_cldr_tiles(A, At, g->cluster_starts, caps, tl, plan.sw.cldr_rows)) return;
+        if (plan.sw.tile_stats)
             fprintf(stderr, "[mgadmm] cldr tiles (geometry %d): %d tiles, rows/tile %.1f, |C1| %.1f, |C2| %.1f (caps %d/%d/%d): reads %.2fx, q recomputed %.2fx\n",
-                    cl_geom, tl.NT, (double)N / tl.NT, (double)tl.sumC1 / tl.NT, (double)tl.sumC2 / tl.NT, caps.Rcap, caps.C1cap, caps.C2cap,
+                    plan.geom, tl.NT, (double)N / tl.NT, (double)tl.sumC1 / tl.NT, (double)tl.sumC2 / tl.NT, caps.Rcap, caps.C1cap, caps.C2cap,
                     (double)tl.sumC2 / N, (double)tl.sumC1 / N);
         std::vector<int> nC((size_t)2 * tl.NT);
         for (int t = 0; t < tl.NT; ++t) { nC[2 * t] = tl.nC1[t]; nC[2 * t + 1] = tl.nC2[t]; }
@@ -306,43 +236,22 @@ struct Engine : EngineBase {
         cldr_dev.NT = tl.NT;
         cldr_dev.state = 1;
     }
-    CldrGeom make_cldr_geom(const Geom& q) const {
-        int vect, nw, ma, mq, mp;
-        cl_dims(vect, nw, ma, mq, mp);
-        CldrGeom cg;
-        cg.T = T; cg.N = N; cg.B = q.B; cg.Bp = q.Bp;
-        while (q.Bp % (64 * vect)) vect /= 2;              // never happens: Bp is padded to the solver's own vector width
-        cg.CH = q.Bp / (64 * vect);
-        cg.NT = cldr_dev.NT;
-        cg.TPX = (cg.NT + 7) / 8;
-        cg.P = 8 * cg.TPX;
-        cg.grid = cg.P * cg.CH;
-        cg.tile_major = cldr_tile_major;
-        cg.q1 = g->q1;
-        cg.lds_bytes = (int)((size_t)nw * (mp + mq) * 64 * vect * sizeof(S));
-        return cg;
-    }
-    // the fused kernel needs Bp to be a multiple of its own chunk width (float64: chunks of at most 128 columns)
-    bool cldr_width_fits(const Geom& q) const {
-        int vect, nw, ma, mq, mp;
-        cl_dims(vect, nw, ma, mq, mp);
-        return q.Bp % (64 * vect) == 0 && (sizeof(S) == 4 || vect <= 2);
-    }
-    bool cldr_fits(const Geom& q) { return cldr_usable() && cldr_width_fits(q); }
+    bool cldr_fits(const Geom& q) { return plan.fused(q, cldr_tiles()); }
     template <class G, template <typename, int> class E, template <typename, int> class SRC, class... A>
     int rows_cldr_g(const Geom& q, const SRC<S, G::VECT>& src, const int* live, A... a) {
+        const int cl_gd = cldr_dev.gd, cl_gt = cldr_dev.gt;      // (streamplan::cldr_slots)
         if (cl_gt == 12) return cl_gd == 6 ? rows_cldr_gd<G, 6, 12, E, SRC>(q, src, live, a...) : rows_cldr_gd<G, 8, 12, E, SRC>(q, src, live, a...);
         if (cl_gt == 16) return cl_gd == 6 ? rows_cldr_gd<G, 6, 16, E, SRC>(q, src, live, a...) : rows_cldr_gd<G, 8, 16, E, SRC>(q, src, live, a...);
         return cl_gd == 6 ? rows_cldr_gd<G, 6, 24, E, SRC>(q, src, live, a...) : rows_cldr_gd<G, 8, 24, E, SRC>(q, src, live, a...);
     }
     template <class G, int GD, int GT, template <typename, int> class E, template <typename, int> class SRC, class... A>
     int rows_cldr_gd(const Geom& q, const SRC<S, G::VECT>& src, const int* live, A... a) {
-        const CldrGeom cg = make_cldr_geom(q);
+        const CldrGeom cg = plan.make_cldr_geom(q, cldr_dev.NT);
         CldrMeta mm{cldr_dev.n0, cldr_dev.nC, cldr_dev.rows, cldr_dev.dcol, cldr_dev.dw, cldr_dev.dcnt, cldr_dev.tcol, cldr_dev.tw, cldr_dev.tcnt};
         typedef E<S, G::VECT> Epi;
         auto fn = k_cldr<S, G::VECT, Epi, SRC<S, G::VECT>, G::NW, G::MA, G::MQ, G::MP, GD, GT, G::MINW>;
-        MG_TRY(allow_dynamic_lds((const void*)fn, 150 * 1024));
-        stream_keys.note(stream_key(STREAM_K_CLDR, IS_F64, G::VECT, Epi::ID, SRC<S, G::VECT>::FOLD, G::NW, G::MA, G::MQ, G::MP, GD, GT, G::MINW));
+        MG_TRY(allow_dynamic_lds((const void*)fn, streamplan::CLDR_LDS_LIMIT));
+        stream_keys.note(plan.key(plan.cldr_choice(GD, GT), Epi::ID, SRC<S, G::VECT>::FOLD));
         hipLaunchKernelGGL(fn, dim3(cg.grid), dim3(G::NW * 64), cg.lds_bytes, st, cg, mm, src, Epi{a...}, partials, live);
         cur_P = cg.P;
         return MGADMM_OK;
@@ -352,7 +261,7 @@ struct Engine : EngineBase {
         const bool timed = prof_open(tag, bytes);
         int rc;
         if constexpr (sizeof(S) == 4) {
-            switch (cl_geom) {
+            switch (plan.geom) {
                 case 1: rc = rows_cldr_g<ClG1, E, SRC>(q, mk_src(ClG1()), live, a...); break;
                 case 3: rc = rows_cldr_g<ClG3, E, SRC>(q, mk_src(ClG3()), live, a...); break;
                 case 4: rc = rows_cldr_g<ClG4, E, SRC>(q, mk_src(ClG4()), live, a...); break;
@@ -382,8 +291,8 @@ struct Engine : EngineBase {
 
     int ensure_partials(const Geom& q) {
         TileGeom tg;
-        int pmax = make_tile_geom(q, tg) ? std::max(q.P, tg.P) : q.P;
-        if (cldr_fits(q)) pmax = std::max(pmax, make_cldr_geom(q).P);
+        int pmax = plan.make_tile_geom(q, tg) ? std::max(q.P, tg.P) : q.P;
+        if (cldr_fits(q)) pmax = std::max(pmax, plan.make_cldr_geom(q, cldr_dev.NT).P);
         size_t need = (size_t)NRED_MAX * pmax * q.Bp;
         if (need <= partials_elems) return MGADMM_OK;
         MG_HIP(hipStreamSynchronize(st));
@@ -398,15 +307,9 @@ struct Engine : EngineBase {
     // the workspace and the buffers of the streaming path, which the LDS path borrows (LdsEngine::init plans after it)
     int init_workspace() {
         MG_HIP(hipSetDevice(g->device));
-        if (const char* e = getenv("MGADMM_WANT_BLOCKS")) want_blocks = std::max(64, atoi(e));
-        if (const char* e = getenv("MGADMM_TILE")) use_tile = atoi(e);
-        if (const char* e = getenv("MGADMM_FUSED")) use_fused = atoi(e);
-        if (const char* e = getenv("MGADMM_FOLD")) use_fold = atoi(e);
-        if (const char* e = getenv("MGADMM_FOLD_LU")) use_fold_lu = atoi(e);
-        if (const char* e = getenv("MGADMM_SWEEP_REV")) sweep_rev = atoi(e);
-        if (const char* e = getenv("MGADMM_CLDR_ORDER")) cldr_tile_major = atoi(e);
+        plan = streamplan::Planner(plan_facts(), streamplan::Switches::from_env((int)sizeof(S)));
         if (const char* e = getenv("MGADMM_LDS_CHUNK")) lds_chunk = std::max(1, std::min(atoi(e), LDS_MAXJ));
-        Geom q = make_geom(Bmax);
+        Geom q = plan.make_geom(Bmax);
         Bp_max = q.Bp;
         // Bp for smaller batches never exceeds Bp_max rounded to 256
         Bp_max = std::max(Bp_max, ((Bmax + 63) / 64) * 64);
@@ -556,7 +459,7 @@ struct Engine : EngineBase {
         bs_Bp = 0;
         if (bs.B == 0) return MGADMM_OK;
         std::vector<float> exp;
-        const int Bp = make_geom(bs.B).Bp;
+        const int Bp = plan.make_geom(bs.B).Bp;
         bs.expand(Bp, exp);
         if (hipMalloc(&d_bs_exp, sizeof(float) * exp.size()) != hipSuccess ||
             hipMemcpy(d_bs_exp, exp.data(), sizeof(float) * exp.size(), hipMemcpyHostToDevice) != hipSuccess) {
@@ -590,18 +493,14 @@ struct Engine : EngineBase {
             case MGADMM_Q_LDS_ROWS: *out = lds.NR; break;
             // (tables prepared by the first operator application; 0 as well when they exist but the batch the solver was created
             // for is no multiple of the kernel's chunk width: the two-pass form runs)
-            case MGADMM_Q_CLDR_SLOTS: *out = cldr_dev.state == 1 && cldr_width_fits(make_geom(Bmax)) ? cl_gt : 0; break;
+            case MGADMM_Q_CLDR_SLOTS: *out = cldr_dev.state == 1 && plan.cldr_width_fits(plan.make_geom(Bmax)) ? cldr_dev.gt : 0; break;
             case MGADMM_Q_LDS_INSTANCE: *out = lds_instance; break;
             case MGADMM_Q_LDS_UNIT: *out = lds_unit; break;
             case MGADMM_Q_LDS_CG_BARRIERS: *out = lds.ok ? lds.cg_barriers : 0; break;
             case MGADMM_Q_NNZ_U: *out = g->hWu.nnz(); break;
             case MGADMM_Q_NNZ_D: *out = g->hWd.nnz(); break;
             case MGADMM_Q_NNZ_DT: *out = g->hWdT.nnz(); break;
-            case MGADMM_Q_TILE_ROWS: {
-                TileGeom tg;
-                *out = make_tile_geom(make_geom(Bmax), tg) ? tg.R : 0;
-                break;
-            }
+            case MGADMM_Q_TILE_ROWS: *out = plan.tile_rows(); break;
             case MGADMM_Q_STREAM_KEYS: *out = (int64_t)stream_keys.keys.size(); break;
             default:
                 if (what >= MGADMM_Q_STREAM_KEY0 && (size_t)(what - MGADMM_Q_STREAM_KEY0) < stream_keys.keys.size()) {
@@ -683,10 +582,8 @@ struct Engine : EngineBase {
     double pass_bytes(const Geom& q, int passes) const { return (double)passes * q.B * (double)T * N * sizeof(S); }
     double csr_bytes(const OpDesc& op) const {
         if (op.kind != OPK_SPATIAL) return 0.0;
-        int nnz = 0;
-        if (op.rowptr == g->Wu.rowptr) nnz = g->Wu.nnz;
-        else if (op.rowptr == g->Wd.rowptr) nnz = g->Wd.nnz;
-        else nnz = g->WdT.nnz;
+        const streamplan::Mat m = mat_of(op);
+        const int nnz = m == streamplan::M_WU ? g->Wu.nnz : (m == streamplan::M_WD ? g->Wd.nnz : g->WdT.nnz);
         return (double)nnz * 8 + (double)(N + 1) * 4;
     }
 
@@ -706,30 +603,24 @@ struct Engine : EngineBase {
     template <class E>
     struct is_elementwise<E, std::void_t<decltype(E::ELEMENTWISE)>> : std::true_type {};
 
+    // The ladders below turn a streamplan::Choice into a kernel instance; which one: the rules of stream_plan.h
     template <int VEC, class Epi, int TGW>
-    int launch_tile(const TileGeom& tg, const OpDesc& op, const TileMeta& tmv, const S* in, const Epi& epi, const int* live) {
-        return tg.R == 20 ? launch_tile2<VEC, Epi, TGW, 5>(tg, op, tmv, in, epi, live)
-                          : launch_tile2<VEC, Epi, TGW, 2>(tg, op, tmv, in, epi, live);
+    int launch_tile(const streamplan::Choice& c, const TileGeom& tg, const OpDesc& op, const TileMeta& tmv, const S* in, const Epi& epi, const int* live) {
+        return c.MR == 5 ? launch_tile2<VEC, Epi, TGW, 5>(c, tg, op, tmv, in, epi, live)
+                         : launch_tile2<VEC, Epi, TGW, 2>(c, tg, op, tmv, in, epi, live);
     }
     template <int VEC, class Epi, int TGW, int MR>
-    int launch_tile2(const TileGeom& tg, const OpDesc& op, const TileMeta& tmv, const S* in, const Epi& epi, const int* live) {
+    int launch_tile2(const streamplan::Choice& c, const TileGeom& tg, const OpDesc& op, const TileMeta& tmv, const S* in, const Epi& epi, const int* live) {
         auto fn = k_tile<S, VEC, Epi, TGW, MR>;
         MG_TRY(allow_dynamic_lds((const void*)fn, 80 * 1024));
-        stream_keys.note(stream_key(STREAM_K_TILE, IS_F64, VEC, Epi::ID, false, TGW, MR));
+        stream_keys.note(plan.key(c, Epi::ID, false));
         hipLaunchKernelGGL(fn, dim3(tg.grid), dim3(256), tg.lds_bytes, st, tg, op, tmv.tl_col, tmv.tl_w, tmv.halo, tmv.h_rowptr,
                            tmv.h_col, tmv.h_val, in, epi, partials, live, TileSrcPlain<S, VEC>());
         return MGADMM_OK;
     }
 
-    // ---- Lu with the CG vector update folded into its loads (k_tile with TileSrcFold): zu solve.  Built for the
-    // production shape only (k = 4 table: 4 slots per row; 8-row tiles; the solver's widest vector): other shapes keep
-    // the separate EpiPUpdate launch.
+    // ---- Lu with the CG vector update folded into its loads (k_tile with TileSrcFold): zu solve, where plan.fold2 says so
     static constexpr int LU_FOLD_VEC = sizeof(S) == 4 ? 4 : 2;
-    bool lu_fold_fits(const Geom& q) {
-        TileGeom tg;
-        if (!use_fold || !use_fold_lu || !use_tile || g->reorder < 2 || q.VEC != LU_FOLD_VEC || g->Wu.max_row > 4) return false;
-        return make_tile_geom(q, tg) && tg.R != 20;
-    }
     template <template <typename, int> class E, class... A>
     int rows_lu_fold(const Geom& q, const S* r, const S* p_old, S* p_new, S* x, const int* live, int tag, int passes, A... a) {
         constexpr int VEC = LU_FOLD_VEC;
@@ -737,13 +628,14 @@ struct Engine : EngineBase {
         typedef TileSrcFold<S, VEC> Src;
         const OpDesc op = g->op_lu();
         const bool timed = prof_open(tag, pass_bytes(q, passes) + csr_bytes(op));
+        const streamplan::Choice c = plan.lu_fold_choice();
         TileGeom tg;
-        if (!make_tile_geom(q, tg)) { mg_set_error("rows_lu_fold: no tile geometry"); return MGADMM_ERR_INVALID; }
+        if (!plan.make_tile_geom(q, tg)) { mg_set_error("rows_lu_fold: no tile geometry"); return MGADMM_ERR_INVALID; }
         TileMeta tmv;
         MG_TRY(tile_meta(0, tg.R, 4, tmv));
         auto fn = k_tile<S, VEC, Epi, 4, 2, Src>;
         MG_TRY(allow_dynamic_lds((const void*)fn, 80 * 1024));
-        stream_keys.note(stream_key(STREAM_K_TILE, IS_F64, VEC, Epi::ID, true, 4, 2));
+        stream_keys.note(plan.key(c, Epi::ID, true));
         hipLaunchKernelGGL(fn, dim3(tg.grid), dim3(256), tg.lds_bytes, st, tg, op, tmv.tl_col, tmv.tl_w, tmv.halo, tmv.h_rowptr,
                            tmv.h_col, tmv.h_val, r, Epi{a...}, partials, live, Src{p_old, p_new, x, d_alpha, d_beta});
         cur_P = tg.P;
@@ -753,29 +645,26 @@ struct Engine : EngineBase {
     }
 
     template <int VEC, int GW, class Epi>
-    int rows_v(const Geom& q, const OpDesc& op, const S* in, const Epi& epi, const int* live, int tag, double bytes) {
+    int rows_v(const Geom& q, const streamplan::Choice& c, const OpDesc& op, const S* in, const Epi& epi, const int* live, int tag, double bytes) {
         const bool timed = prof_open(tag, bytes);
-        TileGeom tg;
-        if (op.kind == OPK_SPATIAL && op.self_w == nullptr && make_tile_geom(q, tg)) {
+        if (c.kernel == STREAM_K_TILE) {
             if constexpr (is_elementwise<Epi>::value) {
                 mg_set_error("rows: element-wise epilogue launched with a spatial operator");
                 return MGADMM_ERR_INVALID;
             } else {
-                const int which = op.rowptr == g->Wu.rowptr ? 0 : (op.rowptr == g->Wd.rowptr ? 1 : 2);
-                // neighbour slots kept in VGPR lanes: 4 for W_u (k = 4), 6 for W_d, 8 for the ragged W_d^T rows
-                const DevCsr& dc = which == 0 ? g->Wu : (which == 1 ? g->Wd : g->WdT);
-                const int tgw = dc.max_row <= 4 ? 4 : (which == 2 || dc.max_row > 6 ? 8 : 6);
+                TileGeom tg;
+                plan.make_tile_geom(q, tg);
                 TileMeta tmv;
-                MG_TRY(tile_meta(which, tg.R, tgw, tmv));
-                switch (tgw) {
-                    case 4: MG_TRY((launch_tile<VEC, Epi, 4>(tg, op, tmv, in, epi, live))); break;
-                    case 6: MG_TRY((launch_tile<VEC, Epi, 6>(tg, op, tmv, in, epi, live))); break;
-                    default: MG_TRY((launch_tile<VEC, Epi, 8>(tg, op, tmv, in, epi, live))); break;
+                MG_TRY(tile_meta(c.mat - streamplan::M_WU, tg.R, c.GW, tmv));
+                switch (c.GW) {
+                    case 4: MG_TRY((launch_tile<VEC, Epi, 4>(c, tg, op, tmv, in, epi, live))); break;
+                    case 6: MG_TRY((launch_tile<VEC, Epi, 6>(c, tg, op, tmv, in, epi, live))); break;
+                    default: MG_TRY((launch_tile<VEC, Epi, 8>(c, tg, op, tmv, in, epi, live))); break;
                 }
                 cur_P = tg.P;
             }
         } else {
-            stream_keys.note(stream_key(STREAM_K_ROWS, IS_F64, VEC, Epi::ID, false, GW));
+            stream_keys.note(plan.key(c, Epi::ID, false));
             hipLaunchKernelGGL((k_rows<S, VEC, Epi, GW>), dim3(q.grid), dim3(256), 0, st, q, op, op.rowptr, op.col, op.val,
                                op.band_w, in, epi, partials, live);
             cur_P = q.P;
@@ -785,30 +674,24 @@ struct Engine : EngineBase {
         return MGADMM_OK;
     }
 
-    // gather window of the row kernel: 4 in-flight neighbour rows for the k=4 spatial Laplacian, 6 otherwise
-    int gather_width(const OpDesc& op) const {
-        if (op.kind != OPK_SPATIAL) return 4;
-        int mr = op.rowptr == g->Wu.rowptr ? g->Wu.max_row : (op.rowptr == g->Wd.rowptr ? g->Wd.max_row : g->WdT.avg_row_ceil);
-        return mr <= 4 ? 4 : 6;
-    }
-
     template <template <typename, int> class E, class... A>
     int rows(const Geom& q, const OpDesc& op, const S* in, const int* live, int tag, int passes, A... a) {
         const double bytes = pass_bytes(q, passes) + csr_bytes(op);
-        const bool wide = gather_width(op) > 4;
-        switch (q.VEC) {
+        const streamplan::Choice c = plan.choose(mat_of(op), op.self_w != nullptr, q);
+        const bool wide = c.kernel == STREAM_K_ROWS && c.GW > 4;      // (k_tile: GW is its slot count, switched on in rows_v)
+        switch (c.VEC) {
             case 1:
-                return wide ? rows_v<1, 6>(q, op, in, E<S, 1>{a...}, live, tag, bytes)
-                            : rows_v<1, 4>(q, op, in, E<S, 1>{a...}, live, tag, bytes);
+                return wide ? rows_v<1, 6>(q, c, op, in, E<S, 1>{a...}, live, tag, bytes)
+                            : rows_v<1, 4>(q, c, op, in, E<S, 1>{a...}, live, tag, bytes);
             case 2:
-                return wide ? rows_v<2, 6>(q, op, in, E<S, 2>{a...}, live, tag, bytes)
-                            : rows_v<2, 4>(q, op, in, E<S, 2>{a...}, live, tag, bytes);
+                return wide ? rows_v<2, 6>(q, c, op, in, E<S, 2>{a...}, live, tag, bytes)
+                            : rows_v<2, 4>(q, c, op, in, E<S, 2>{a...}, live, tag, bytes);
             case 4:
                 if constexpr (sizeof(S) == 4)
-                    return wide ? rows_v<4, 6>(q, op, in, E<S, 4>{a...}, live, tag, bytes)
-                                : rows_v<4, 4>(q, op, in, E<S, 4>{a...}, live, tag, bytes);
+                    return wide ? rows_v<4, 6>(q, c, op, in, E<S, 4>{a...}, live, tag, bytes)
+                                : rows_v<4, 4>(q, c, op, in, E<S, 4>{a...}, live, tag, bytes);
         }
-        mg_set_error("rows: unsupported VEC %d", q.VEC);
+        mg_set_error("rows: unsupported VEC %d", c.VEC);
         return MGADMM_ERR_UNSUPPORTED;
     }
 
@@ -946,11 +829,11 @@ struct Engine : EngineBase {
             else nact_cur = 0;
         }
         const int base = nact_locked ? NACT_LOG : nact_cur;
-        // kind 1 on the fused kernel: the vector update of iteration k (p = r + beta p, x += alpha p) is folded into the
-        // SpMM launch of iteration k+1 (k_cldr with CldrSrcFold); p alternates between two buffers because other tiles
-        // still gather the old direction for their halos.  The x update of the last iteration is applied after the loop.
-        const bool fold1 = d.kind == 1 && use_fold && cldr_fits(q);
-        const bool fold2 = d.kind == 2 && lu_fold_fits(q);      // zu solve: the same fold in the LDS-tiled Lu kernel
+        // the vector update of iteration k folded into the SpMM launch of iteration k+1 (k_cldr / k_tile, stream_plan.h): p
+        // alternates between two buffers because other tiles still gather the old direction for their halos.  The x update
+        // of the last iteration is applied after the loop.
+        const bool fold1 = plan.fold1(d.kind, q, d.kind == 1 ? cldr_tiles() : 0);
+        const bool fold2 = plan.fold2(d.kind, q);
         const bool fold = fold1 || fold2;
         S* pbuf[2] = {pp, vec[V_Q]};          // V_Q is free: the fused kernel keeps q = Ldr p on chip
         int k = 0;
@@ -973,7 +856,7 @@ struct Engine : EngineBase {
                 // r -= alpha Ap, r.r -- swept from the LAST time slice down: the SpMM kernel before it finished with the
                 // last slices of Ap (still in the Infinity Cache), and the kernel after it starts with the first slices of r
                 Geom qr = q;
-                qr.rev = sweep_rev;
+                qr.rev = plan.sw.sweep_rev;
                 MG_TRY(rows<EpiCgUpdate>(qr, op_none(), Ap, live, 1, 3, (const S*)d_alpha, r));
             }
             MG_TRY((reduce<1>(q, FinCgBeta<S>{c, k, q.Bp, p.cg_tol, batch_max}, live)));
@@ -1011,7 +894,7 @@ struct Engine : EngineBase {
         MG_TRY(check_B(B, "apply"));
         MG_REQUIRE(x && y, "apply: null pointer");
         st = s;
-        Geom q = make_geom(B);
+        Geom q = plan.make_geom(B);
         MG_TRY(ensure_partials(q));
         MG_TRY(pack(q, x, T, vec[V_IO0]));
         switch (op) {
@@ -1031,7 +914,7 @@ struct Engine : EngineBase {
         MG_REQUIRE(which >= 0 && which <= 2, "lhs: bad operator id %d", which);
         MG_REQUIRE(!(which == MGADMM_LHS_ZD && p.ablation == MGADMM_ABL_DGLR), "lhs: LHS_zd is undefined for ablation 'DGLR' (ADMM.py:392-399)");
         st = s;
-        Geom q = make_geom(B);
+        Geom q = plan.make_geom(B);
         MG_TRY(ensure_partials(q));
         MG_TRY(pack(q, x, T, vec[V_IO0]));
         const S* m = nullptr;
@@ -1047,7 +930,7 @@ struct Engine : EngineBase {
         MG_TRY(check_B(B, "phi_direct"));
         MG_REQUIRE(x && gamma && phi, "phi_direct: null pointer");
         st = s;
-        Geom q = make_geom(B);
+        Geom q = plan.make_geom(B);
         MG_TRY(ensure_partials(q));
         MG_TRY(pack(q, x, T, vec[V_IO0]));
         MG_TRY(pack(q, gamma, T, vec[V_TMP]));
@@ -1086,7 +969,7 @@ struct Engine : EngineBase {
         MG_TRY(check_B(B, "initial_guess"));
         MG_REQUIRE(x && y, "initial_guess: null pointer");
         st = s;
-        Geom q = make_geom(B);
+        Geom q = plan.make_geom(B);
         MG_TRY(pack(q, y, p.t_in, vec[V_Y]));
         MG_TRY(guess_internal(q, vec[V_Y], vec[V_IO1]));
         return unpack(q, vec[V_IO1], x);
@@ -1096,7 +979,7 @@ struct Engine : EngineBase {
         MG_TRY(check_B(B, "initial_interpolation"));
         MG_REQUIRE(x && y && mask, "initial_interpolation: null pointer");
         st = s;
-        Geom q = make_geom(B);
+        Geom q = plan.make_geom(B);
         MG_TRY(pack(q, y, T, vec[V_Y]));
         MG_TRY(pack(q, mask, T, vec[V_MASK]));
         MG_TRY(interp_internal(q, vec[V_Y], vec[V_MASK], mask_f32, vec[V_IO1]));
@@ -1120,7 +1003,7 @@ struct Engine : EngineBase {
         MG_REQUIRE(which >= 0 && which <= 2, "cg: bad operator id %d", which);
         MG_REQUIRE(!(which == MGADMM_LHS_ZD && p.ablation == MGADMM_ABL_DGLR), "cg: LHS_zd is undefined for ablation 'DGLR'");
         st = s;
-        Geom q = make_geom(B);
+        Geom q = plan.make_geom(B);
         MG_TRY(ensure_partials(q));
         MG_HIP(hipMemsetAsync(d_nonfinite, 0, sizeof(int), st));
         MG_TRY(pack(q, rhs, T, vec[V_RHS]));
@@ -1263,7 +1146,7 @@ struct Engine : EngineBase {
         MG_TRY(refused(bandsets::solve_gate(bs, facts(p), B)));                // (a band table: after every refusal of solve_gate)
         if (use_lds()) return solve_lds(y, mask, B, x0, state_in, x_out, state_out, hist);
         MG_TRY(refused(solvegate::admm_convergence_gate(facts(p), "solve")));       // (refused at solver_create / set_params already)
-        const Geom q = make_geom(B);
+        const Geom q = plan.make_geom(B);
         // a band table: the Ldr / Ldr^T of this solve read a weight per batch column (op_ldr, op_ldrt) until it returns
         struct BandScope { const float*& wb; ~BandScope() { wb = nullptr; } } band_scope{band_wb};
         if (bs.B > 0) {
@@ -1356,7 +1239,7 @@ struct Engine : EngineBase {
         MG_REQUIRE(y && x_out, "two_loops: null pointer");
         MG_REQUIRE(p.max_inner_iter >= 1, "two_loops: max_inner_iter must be >= 1 (got %d)", p.max_inner_iter);
         st = s;
-        const Geom q = make_geom(B);
+        const Geom q = plan.make_geom(B);
         MG_TRY(ensure_partials(q));
         const size_t ne = velems(q);
         const bool has_phi = this->has_phi(), has_zd = this->has_zd();

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "stream_geom.h"
 #include "tile_meta.h"
 
 template <typename S, int V>
@@ -94,19 +95,6 @@ template <typename S, int V>
 __device__ __forceinline__ void sto(S* p, size_t off, const Vec<S, V>& x) { stv<S, V>(p + off, x); }
 template <typename S, int V>
 __device__ __forceinline__ void sto(S* p, const OffSplit& o, const Vec<S, V>& x) { stv_u<S, V>(p + o.u, o.lb, x); }
-
-struct Geom {
-    int T, N, B, Bp;
-    int VEC, CH;         // columns per lane; column chunks of 64*VEC
-    int RI;              // rows per work item
-    int NX, NBL;         // node rows owned by one XCD (multiple of RI); work items per time slice and XCD
-    int n_items;         // T * NBL work items per (XCD, column chunk), enumerated t-major
-    int G8;              // workgroups per (XCD, column chunk)
-    int P;               // partial-sum rows per column = 8 * G8 (one per workgroup of a chunk)
-    int grid;            // 8 * G8 * CH workgroups
-    int rev;             // 1: sweep the time slices from T-1 down to 0 (see Engine::cg_internal: the slices a kernel touches
-                         //    LAST are the ones still in the 256 MiB Infinity Cache when the next kernel starts)
-};
 
 constexpr int CSR_PAD = 8;     // col/val arrays carry this many extra entries (reads past a row end are safe)
 
@@ -369,16 +357,6 @@ __global__ __launch_bounds__(256) void k_rows(Geom g, OpDesc op, const int* __re
 // are requested while step s computes; the epilogue functors are the ones of k_rows.  The kernel is
 // latency-bound (VALU ~25 %, LDS ~15-30 % busy, waits > 50 %): small tiles / many resident workgroups win.
 // ---------------------------------------------------------------------------------------------
-struct TileGeom {
-    int T, N, B, Bp;
-    int VEC, CH;
-    int R;        // node rows per tile (<= 4 * TILE_MAXR)
-    int NTILE;    // tiles per column chunk
-    int TPX;      // tile slots per XCD = ceil(NTILE / 8)
-    int P;        // partial rows per column = 8 * TPX
-    int grid;     // 8 * TPX * CH workgroups
-    int lds_bytes;
-};
 constexpr int TILE_MAXR = 8;    // rows per wave and time step (4 waves -> R <= 32)
 constexpr int TILE_GW_MAX = 8;  // neighbour slots per row held in VGPR lanes: 4 (W_u), 6 (W_d) or 8 (W_d^T); MAXR*GW <= 64
 // TILE_HMAX (tile_meta.h): halo rows (out-of-tile neighbours) staged in LDS per tile and step
@@ -708,18 +686,6 @@ __global__ __launch_bounds__(256) void k_tile(TileGeom g, OpDesc op, const int* 
 // in k_tile (tables built on the host by build_cldr_tiles, cldr_tiles.h, which has a CPU replay test).  Sums run in
 // CSR entry order and q is rounded to S like the stored q of the two-pass form: the result is BITWISE the same.
 // ---------------------------------------------------------------------------------------------
-struct CldrGeom {
-    int T, N, B, Bp;
-    int CH;           // column chunks of 64*VECT
-    int NT;           // tiles
-    int TPX;          // tile slots per XCD = ceil(NT / 8)
-    int P;            // partial rows per column = 8 * TPX
-    int grid;         // 8 * TPX * CH workgroups
-    int tile_major;   // 1: consecutive workgroups of an XCD take consecutive TILES of one chunk (shared halos stay hot in
-                      //    its L2); 0: consecutive workgroups take the CHUNKS of one tile (whole rows are consumed together)
-    int q1;           // quirk Q1 self coefficient at t = 0 (immaterial: q_0 = 0)
-    int lds_bytes;
-};
 struct CldrMeta {
     const int* n0;     // [NT+1]
     const int* nC;     // [NT][2]  |C1|, |C2|

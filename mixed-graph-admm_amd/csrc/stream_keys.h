@@ -1,7 +1,8 @@
 // Instance keys of the streaming-path kernels (k_rows, k_tile, k_cldr in stream_kernels.h).  Plain C++, no HIP: the launch
-// sites of engine.h pack the template arguments of what they launch into one int64 and keep the distinct keys of a solver in
-// first-launch order (MGADMM_Q_STREAM_KEYS / MGADMM_Q_STREAM_KEY0 + i); mgadmm/_lib.py (decode_stream_key) turns a key back
-// into the name `nm -C` prints for the instance.  Tests only: the cost is a linear search over a few dozen keys per launch.
+// sites of engine.h note the key of the instance the plan chose (stream_plan.h, Planner::key: the template arguments packed
+// into one int64) and keep the distinct keys of a solver in first-launch order (MGADMM_Q_STREAM_KEYS / MGADMM_Q_STREAM_KEY0
+// + i); mgadmm/_lib.py (decode_stream_key) turns a key back into the name `nm -C` prints for the instance.  Tests only: the
+// cost is a linear search over a few dozen keys per launch.
 //
 //   bits  0 ..  1   kernel: 0 k_rows, 1 k_tile, 2 k_cldr
 //   bit   2         scalar type: 0 float, 1 double

@@ -1,12 +1,14 @@
-"""Census of the streaming path (k_rows, k_tile, k_cldr of csrc/stream_kernels.h; dispatch in csrc/engine.h): one row per
+"""Census of the streaming path (k_rows, k_tile, k_cldr of csrc/stream_kernels.h; the dispatch rules in csrc/stream_plan.h, the
+launch ladders that follow them in csrc/engine.h): one row per
 PROBLEM, with the set of kernel instances the problem must launch.  tests/test_stream_census_cpu.py proves that the union of
 the rows' sets plus the UNREACHABLE table is exactly what the built library ships; tests/test_gpu_stream_census.py runs every
 row against the float64 oracle and asserts, through MGADMM_Q_STREAM_KEYS, that the named instances really ran.
 
-The expected set of a row is not a recording: `expected(r)` restates the dispatch of engine.h (rows / rows_v / launch_tile /
-rows_lu_fold / rows_cldr_*) from the row's dtype, batch, switches and the row lengths of its three matrices, call by call of
-the phases the GPU test runs (operators, left-hand sides, CG solves, the ADMM loop).  The GPU test asserts equality, so a
-change of the dispatch shows up as a named difference."""
+The expected set of a row is not a recording: `expected(r)` restates the dispatch (streamplan::Planner of stream_plan.h: choose,
+fused, fold1 / fold2, lu_fold_fits; the call sites of engine.h) from the row's dtype, batch, switches and the row lengths of
+its three matrices, call by call of the phases the GPU test runs (operators, left-hand sides, CG solves, the ADMM loop).  The
+GPU test asserts equality, so a change of the dispatch shows up as a named difference; tests/test_stream_plan_cpu.py compares
+the planner itself with this model on the CPU."""
 import os
 import re
 
@@ -88,9 +90,9 @@ def row_lengths(r):
     return int(lens.max()), int(lens.max()) + 1, int(indeg.max()), -(-int(lens.sum() + N) // N)
 
 
-# ------------------------------------------------------------------------------------------- the dispatch of engine.h
+# ------------------------------------------------------------------------- the dispatch of stream_plan.h and engine.h
 def cldr_geoms():
-    """{geometry: (VECT, NW, MA, MQ, MP)} read from CLDR_GEOMS in csrc/cldr_tiles.h, the table engine.h builds ClG1 ... ClG4 from."""
+    """{geometry: (VECT, NW, MA, MQ, MP)} read from CLDR_GEOMS in csrc/cldr_tiles.h, the table stream_plan.h reads and engine.h builds ClG1 ... ClG4 from."""
     hdr = open(os.path.join(PKG, "csrc", "cldr_tiles.h")).read()
     body = re.search(r"CLDR_GEOMS\[\d+\]\s*=\s*\{(.*?)\};", hdr, re.S).group(1)
     rows = re.findall(r"\{\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*\}", body)
@@ -102,7 +104,7 @@ ABL_HAS_PHI = {"None": True, "DGLR": True, "DGTV": False, "UT": False}
 
 
 def vec_of(dtype, B):
-    """Engine::make_geom: columns per lane and the padded batch."""
+    """streamplan::Planner::make_geom: columns per lane and the padded batch."""
     if dtype == "f32":
         v = 4 if B >= 192 else 2 if B >= 96 else 1
     else:
@@ -134,7 +136,7 @@ class Dispatch:
 
     # --- launch sites
     def rows(self, epi, op):
-        """Engine::rows + rows_v.  op: 'none' | 'band' | 'lu' | 'ldr' | 'ldrt', '+self' for the operators of Ln (self_w set)."""
+        """Planner::choose (launched by Engine::rows + rows_v).  op: 'none' | 'band' | 'lu' | 'ldr' | 'ldrt', '+self' for the operators of Ln (self_w set)."""
         S, V = self.S, self.VEC
         base, own_self = op.split("+")[0], op.endswith("+self")
         if not self.spatial and base in ("ldr", "ldrt"):
@@ -356,14 +358,16 @@ _fallback_rows()
 assert len({r["name"] for r in CENSUS}) == len(CENSUS)
 
 # ------------------------------------------------------------------------------------------------------ unreachable
-# Shipped instances no problem can launch: (regular expression, the dispatch line that excludes them).  The CPU test
-# requires every shipped name to be in a row's set or to match exactly one of these, and every pattern to match something.
+# Shipped instances no problem can launch: (regular expression, "<file> <function>: the dispatch line there that excludes them").
+# The CPU test requires every shipped name to be in a row's set or to match exactly one of these, every pattern to match
+# something, and the named function to stand in the named file.
 UNREACHABLE = [
     (r"k_tile<.*, EpiAddTo<.*",
-     "engine.h op_ln: EpiAddTo runs with the father operator of Ln only, whose self_w is set; rows_v takes k_tile only for "
-     "op.self_w == nullptr, so Ln always runs k_rows"),
+     "engine.h op_ln: EpiAddTo runs with the father operator of Ln only, whose self_w is set; Planner::choose (stream_plan.h) takes "
+     "k_tile only for an operator without self_w, so Ln always runs k_rows"),
     (r"k_tile<.*, EpiRhsX<[^>]*>, 6, .*",
-     "engine.h solve: the spatial EpiRhsX launch applies op_ldrt (W_d^T); rows_v gives W_d^T 4 or 8 slots, never 6"),
+     "engine.h admm_step: the spatial EpiRhsX launch applies op_ldrt (W_d^T); Planner::choose (stream_plan.h) gives W_d^T 4 or 8 "
+     "slots, never 6"),
     (r"k_rows<.*, Epi(CgUpdate|PUpdate|XFinal|Lin2|Dual|LnLine)<[^>]*>, 6>",
-     "engine.h gather_width: the element-wise epilogues run with op_none (kind != OPK_SPATIAL): gather width 4"),
+     "stream_plan.h choose: the element-wise epilogues run with op_none (no spatial matrix): gather window 4"),
 ]

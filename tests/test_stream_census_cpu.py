@@ -41,7 +41,9 @@ def test_census_and_unreachable_are_exactly_what_the_library_ships(union):
     assert {k: sum(n.startswith(k + "<") for n in shipped) for k in SHIPPED} == SHIPPED
     excluded = {}
     for pat, why in sc.UNREACHABLE:
-        assert why and "engine.h" in why, pat                         # every entry carries the dispatch line that excludes it
+        where = re.match(r"(\w+\.h) (\w+): \S", why)                   # every entry names the file and the function of the dispatch line that excludes it
+        assert where, pat
+        assert re.search(r"\b%s\(" % where.group(2), open(os.path.join(PKG, "csrc", where.group(1))).read()), (pat, where.groups())
         hit = {n for n in shipped if re.fullmatch(pat, n)}
         assert hit, ("stale UNREACHABLE pattern", pat)
         assert not (hit & set(excluded)), ("two UNREACHABLE patterns for one instance", pat)
@@ -199,6 +201,7 @@ def test_key_decoder():
 
 
 def test_dispatch_model_reads_the_engines_numbers():
-    """The geometry table of stream_census.py is parsed from csrc/cldr_tiles.h; the batch thresholds are make_geom's."""
+    """The geometry table of stream_census.py is parsed from csrc/cldr_tiles.h; the batch thresholds are those of make_geom
+    (csrc/stream_plan.h)."""
     assert set(sc.CLDR_GEOMS) == {1, 2, 3, 4} and sc.CLDR_GEOMS[1] == (4, 8, 2, 4, 5)
     assert np.all([sc.vec_of("f32", b)[0] == v for b, v in ((3, 1), (95, 1), (96, 2), (191, 2), (192, 4))])

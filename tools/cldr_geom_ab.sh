@@ -2,7 +2,7 @@
 # k_cldr tile geometries side by side on the cfg3 workload (run from the repo root on the GPU box):
 #   tools/cldr_geom_ab.sh <outdir> <geom> [<geom> ...]
 # per geometry: a kernel-trace pass, a FETCH_SIZE pass and a WRITE_SIZE pass of `bench.py --workload cfg3 --steps 3`, then
-# live launch time and HBM bytes of the k_cldr instances (MGADMM_CLDR_GEOM, engine.h).
+# live launch time and HBM bytes of the k_cldr instances (MGADMM_CLDR_GEOM, stream_plan.h).
 set -u
 out=$1; shift
 mkdir -p $out
