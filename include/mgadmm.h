@@ -401,7 +401,10 @@ int mgadmm_weight_tables(int32_t n_nodes, int32_t k1, const int64_t* connect_lis
  * `series` is the (n_steps, n_cols) row-major device array data[t, node*C + c] of dtype MGADMM_F32/F64.
  * Per-column statistics over time (device outputs of n_cols elements in the series dtype, any may be NULL):
  * min / max (utils.py:87-88), mean and the unbiased standard deviation of torch.std (utils.py:83-84).
- * Fixed-order reductions (bitwise repeatable).  Asynchronous on `stream`. */
+ * Fixed-order reductions (bitwise repeatable).  Asynchronous on `stream`.
+ * A column that holds a NaN gives NaN in all four outputs, as torch.min / torch.max / mean / std do; +inf (-inf) gives
+ * max (min) and mean of that infinity and a NaN std.  At most 16 776 960 time steps (65535 row chunks of 256);
+ * a longer series is refused with MGADMM_ERR_INVALID before anything is allocated. */
 int mgadmm_series_stats(const void* series, int64_t n_steps, int32_t n_cols, int32_t dtype, void* o_min, void* o_max,
                         void* o_mean, void* o_std, void* stream);
 /* In place.  inverse == 0: series = (series - shift[col]) / s[col]; inverse != 0 (recover_data, utils.py:110-118):

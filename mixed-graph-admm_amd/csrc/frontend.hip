@@ -2,13 +2,18 @@
 // solver sees it (utils.py:54-134) -- per-node statistics, standardize / normalize (and recover_data), and the
 // sliding windows data[i : i + 24] / data[i : i + 12] of get_predict_data / get_interpolated_data, for a whole
 // batch of start indices at once.  HBM-bound byte work: coalesced over the node axis, fixed-order reductions.
-#include <algorithm>
-
 #include "common.h"
+#include "frontend_geom.h"
 
 namespace {
 
-constexpr int ST_ROWS = 256;    // time steps per partial (one workgroup row chunk)
+using fegeom::ST_ROWS;          // time steps per partial (one workgroup row chunk)
+
+// min / max that hand a NaN on, as torch.min / torch.max do (the device's min / max return the operand that is no NaN)
+template <typename S>
+__device__ __forceinline__ S nan_min(S a, S v) { return (v < a || v != v) ? v : a; }
+template <typename S>
+__device__ __forceinline__ S nan_max(S a, S v) { return (v > a || v != v) ? v : a; }
 
 // Stage 1: per (row chunk, column) partial min / max / sum.  Block = 64 columns x 4 row lanes; a row lane walks
 // its quarter of the chunk, lanes are combined through LDS in fixed order.
@@ -32,8 +37,8 @@ __global__ __launch_bounds__(256) void k_col_partials(long n_steps, int n_cols, 
                 sum += d * d;
             } else {
                 sum += (double)v;
-                mn = any ? min(mn, v) : v;
-                mx = any ? max(mx, v) : v;
+                mn = any ? nan_min(mn, v) : v;
+                mx = any ? nan_max(mx, v) : v;
                 any = true;
             }
         }
@@ -49,8 +54,8 @@ __global__ __launch_bounds__(256) void k_col_partials(long n_steps, int n_cols, 
         for (int j = 1; j < 4; ++j) {
             t += s_sum[j][cx];
             if (s_any[j][cx]) {
-                a = have ? min(a, s_min[j][cx]) : s_min[j][cx];
-                b = have ? max(b, s_max[j][cx]) : s_max[j][cx];
+                a = have ? nan_min(a, s_min[j][cx]) : s_min[j][cx];
+                b = have ? nan_max(b, s_max[j][cx]) : s_max[j][cx];
                 have = true;
             }
         }
@@ -73,8 +78,8 @@ __global__ __launch_bounds__(256) void k_col_finish(int nchunk, long n_steps, in
     if (mode == 0) {
         S a = pmin[col], b = pmax[col];
         for (int c = 1; c < nchunk; ++c) {
-            a = min(a, pmin[(size_t)c * n_cols + col]);
-            b = max(b, pmax[(size_t)c * n_cols + col]);
+            a = nan_min(a, pmin[(size_t)c * n_cols + col]);
+            b = nan_max(b, pmax[(size_t)c * n_cols + col]);
         }
         const double m = t / (double)n_steps;
         mean_d[col] = m;
@@ -104,7 +109,7 @@ __global__ __launch_bounds__(256) void k_windows(long n_steps, int n_cols, int w
                                                  const float* __restrict__ mask, S* __restrict__ out, int* __restrict__ bad) {
     const int b = blockIdx.y;
     const long long s0 = starts[b];
-    if (s0 < 0 || s0 + win > n_steps) {
+    if (!fegeom::window_in_range(s0, win, n_steps)) {
         if (threadIdx.x == 0 && blockIdx.x == 0) *bad = 1;
         return;
     }
@@ -120,27 +125,42 @@ __global__ __launch_bounds__(256) void k_windows(long n_steps, int n_cols, int w
 
 template <typename S>
 int series_stats(const S* x, int64_t n_steps, int n_cols, S* o_min, S* o_max, S* o_mean, S* o_std, hipStream_t st) {
-    const int nchunk = (int)((n_steps + ST_ROWS - 1) / ST_ROWS);
-    double *psum = nullptr, *mean_d = nullptr;
-    S *pmin = nullptr, *pmax = nullptr;
-    MG_HIP(hipMallocAsync((void**)&psum, sizeof(double) * (size_t)nchunk * n_cols, st));
-    MG_HIP(hipMallocAsync((void**)&mean_d, sizeof(double) * n_cols, st));
-    MG_HIP(hipMallocAsync((void**)&pmin, sizeof(S) * (size_t)nchunk * n_cols, st));
-    MG_HIP(hipMallocAsync((void**)&pmax, sizeof(S) * (size_t)nchunk * n_cols, st));
-    const dim3 g1((n_cols + 63) / 64, nchunk), g2((n_cols + 255) / 256);
-    hipLaunchKernelGGL(k_col_partials<S>, g1, dim3(256), 0, st, (long)n_steps, n_cols, x, (const double*)nullptr, psum, pmin, pmax);
-    hipLaunchKernelGGL(k_col_finish<S>, g2, dim3(256), 0, st, nchunk, (long)n_steps, n_cols, 0, psum, pmin, pmax, mean_d, o_min, o_max,
-                       o_mean, (S*)nullptr);
-    if (o_std) {
-        hipLaunchKernelGGL(k_col_partials<S>, g1, dim3(256), 0, st, (long)n_steps, n_cols, x, (const double*)mean_d, psum, pmin, pmax);
-        hipLaunchKernelGGL(k_col_finish<S>, g2, dim3(256), 0, st, nchunk, (long)n_steps, n_cols, 1, psum, pmin, pmax, mean_d, (S*)nullptr,
-                           (S*)nullptr, (S*)nullptr, o_std);
+    MG_REQUIRE(fegeom::steps_supported(n_steps), "series_stats: at most 16 776 960 time steps (65535 row chunks of %d), got %lld", ST_ROWS,
+               (long long)n_steps);
+    const int nchunk = fegeom::stats_chunks(n_steps);
+    void* buf[4] = {nullptr, nullptr, nullptr, nullptr};      // psum, mean_d, pmin, pmax
+    const size_t bytes[4] = {sizeof(double) * (size_t)nchunk * n_cols, sizeof(double) * n_cols, sizeof(S) * (size_t)nchunk * n_cols,
+                             sizeof(S) * (size_t)nchunk * n_cols};
+    hipError_t err = hipSuccess;
+    const char* what = "hipMallocAsync";
+    for (int k = 0; k < 4 && err == hipSuccess; ++k) err = hipMallocAsync(&buf[k], bytes[k], st);
+    if (err == hipSuccess) {
+        double *psum = (double*)buf[0], *mean_d = (double*)buf[1];
+        S *pmin = (S*)buf[2], *pmax = (S*)buf[3];
+        const fegeom::Grid p1 = fegeom::stats_partials_grid(nchunk, n_cols), p2 = fegeom::stats_finish_grid(n_cols);
+        const dim3 g1(p1.x, p1.y), g2(p2.x, p2.y);
+        hipLaunchKernelGGL(k_col_partials<S>, g1, dim3(256), 0, st, (long)n_steps, n_cols, x, (const double*)nullptr, psum, pmin, pmax);
+        hipLaunchKernelGGL(k_col_finish<S>, g2, dim3(256), 0, st, nchunk, (long)n_steps, n_cols, 0, psum, pmin, pmax, mean_d, o_min, o_max,
+                           o_mean, (S*)nullptr);
+        if (o_std) {
+            hipLaunchKernelGGL(k_col_partials<S>, g1, dim3(256), 0, st, (long)n_steps, n_cols, x, (const double*)mean_d, psum, pmin, pmax);
+            hipLaunchKernelGGL(k_col_finish<S>, g2, dim3(256), 0, st, nchunk, (long)n_steps, n_cols, 1, psum, pmin, pmax, mean_d,
+                               (S*)nullptr, (S*)nullptr, (S*)nullptr, o_std);
+        }
+        err = hipGetLastError();
+        what = "kernel launch";
     }
-    MG_HIP(hipGetLastError());
-    MG_HIP(hipFreeAsync(psum, st));
-    MG_HIP(hipFreeAsync(mean_d, st));
-    MG_HIP(hipFreeAsync(pmin, st));
-    MG_HIP(hipFreeAsync(pmax, st));
+    // the scratch buffers are freed on every way out (stream-ordered: after the kernels that use them)
+    for (int k = 0; k < 4; ++k) {
+        if (!buf[k]) continue;
+        const hipError_t e = hipFreeAsync(buf[k], st);
+        if (err == hipSuccess && e != hipSuccess) { err = e; what = "hipFreeAsync"; }
+    }
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        mg_set_error("series_stats: %s -> %s", what, hipGetErrorString(err));
+        return MGADMM_ERR_HIP;
+    }
     return MGADMM_OK;
 }
 
@@ -179,7 +199,7 @@ extern "C" int mgadmm_series_affine(void* series, int64_t n_steps, int32_t n_col
     MG_TRY(use_device_of(series, "series_affine"));
     hipStream_t st = (hipStream_t)stream;
     const long total = (long)n_steps * n_cols;
-    const dim3 grid((unsigned)std::min<long>((total + 255) / 256, 8192));
+    const dim3 grid(fegeom::affine_grid(total).x);
     if (dtype == MGADMM_F64)
         hipLaunchKernelGGL(k_affine<double>, grid, dim3(256), 0, st, total, n_cols, inverse, (const double*)shift, (const double*)scale,
                            (const double*)scale_lo, (double*)series);
@@ -198,14 +218,15 @@ extern "C" int mgadmm_gather_windows(const void* series, int64_t n_steps, int32_
                                      int32_t win, const float* mask, void* out, void* stream) {
     MG_REQUIRE(series && starts && out && n_steps >= 1 && n_cols >= 1 && B >= 1 && win >= 1, "gather_windows: bad arguments");
     MG_REQUIRE(win <= n_steps, "gather_windows: window of %d steps, series of %lld", win, (long long)n_steps);
-    MG_REQUIRE(B <= 65535, "gather_windows: at most 65535 windows per call, got %d", B);
+    MG_REQUIRE(B <= fegeom::MAX_WINDOWS, "gather_windows: at most 65535 windows per call, got %d", B);
     MG_TRY(use_device_of(series, "gather_windows"));
     hipStream_t st = (hipStream_t)stream;
     int* bad = nullptr;
     MG_HIP(hipMallocAsync((void**)&bad, sizeof(int), st));
     MG_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
     const long per = (long)win * n_cols;
-    const dim3 grid((unsigned)std::min<long>((per + 255) / 256, 64), B);
+    const fegeom::Grid wg = fegeom::windows_grid(per, B);
+    const dim3 grid(wg.x, wg.y);
     if (dtype == MGADMM_F64)
         hipLaunchKernelGGL(k_windows<double>, grid, dim3(256), 0, st, (long)n_steps, n_cols, win, (const double*)series,
                            (const long long*)starts, mask, (double*)out, bad);

@@ -36,7 +36,8 @@ def _check_series(series):
 
 def series_stats(series, std=True):
     """Per-column min, max, mean (and unbiased std) over time of a (T, N[, C]) device series.
-    Returns tensors of shape (1, N[, C]) like `data.max(0, keepdim=True)[0]` etc. (utils.py:83-88)."""
+    Returns tensors of shape (1, N[, C]) like `data.max(0, keepdim=True)[0]` etc. (utils.py:83-88); like them, a column
+    that holds a NaN is NaN in all four.  At most 16 776 960 time steps."""
     n_steps, n_cols = _check_series(series)
     shp = (1,) + tuple(series.shape[1:])
     outs = [torch.empty(shp, dtype=series.dtype, device=series.device) for _ in range(4 if std else 3)]
