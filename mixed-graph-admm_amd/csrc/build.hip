@@ -144,12 +144,6 @@ __global__ __launch_bounds__(256) void k_norm_directed(int n, int k1, const floa
     for (int j = 0; j < k1; ++j) w[(size_t)i * k1 + j] *= inv;
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    template <class T> T* as() { return static_cast<T*>(p); }
-};
-
 }  // namespace
 
 extern "C" int mgadmm_knn_graph(int32_t n_nodes, int64_t n_edges, const int64_t* edges, const double* dists, int32_t k,
@@ -179,30 +173,26 @@ extern "C" int mgadmm_knn_graph(int32_t n_nodes, int64_t n_edges, const int64_t*
     }
     MG_HIP(hipSetDevice(device));
     const int k1 = k + 1;
-    DevBuf d_rp, d_adj, d_w, d_nn, d_nd, d_of;
-    MG_HIP(hipMalloc(&d_rp.p, sizeof(int) * (n_nodes + 1)));
-    MG_HIP(hipMalloc(&d_adj.p, sizeof(int) * std::max<size_t>(adj.size(), 1)));
-    MG_HIP(hipMalloc(&d_w.p, sizeof(double) * std::max<size_t>(w.size(), 1)));
-    MG_HIP(hipMalloc(&d_nn.p, sizeof(int) * (size_t)n_nodes * k1));
-    MG_HIP(hipMalloc(&d_nd.p, sizeof(float) * (size_t)n_nodes * k1));
-    MG_HIP(hipMalloc(&d_of.p, sizeof(int)));
-    MG_HIP(hipMemcpy(d_rp.p, rowptr.data(), sizeof(int) * (n_nodes + 1), hipMemcpyHostToDevice));
-    if (!adj.empty()) {
-        MG_HIP(hipMemcpy(d_adj.p, adj.data(), sizeof(int) * adj.size(), hipMemcpyHostToDevice));
-        MG_HIP(hipMemcpy(d_w.p, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice));
-    }
-    MG_HIP(hipMemset(d_of.p, 0, sizeof(int)));
-    hipLaunchKernelGGL(k_knn_dijkstra, dim3((n_nodes + 63) / 64), dim3(64), 0, 0, n_nodes, k1, d_rp.as<int>(), d_adj.as<int>(),
-                       d_w.as<double>(), d_nn.as<int>(), d_nd.as<float>(), d_of.as<int>());
+    DevBuf<int> d_rp, d_adj, d_nn, d_of;
+    DevBuf<double> d_w;
+    DevBuf<float> d_nd;
+    MG_BUF(d_rp.upload(rowptr));
+    MG_BUF(d_adj.upload(adj));      // (no edges: one element nobody reads)
+    MG_BUF(d_w.upload(w));
+    MG_BUF(d_nn.reserve((size_t)n_nodes * k1));
+    MG_BUF(d_nd.reserve((size_t)n_nodes * k1));
+    MG_BUF(d_of.upload({0}));
+    hipLaunchKernelGGL(k_knn_dijkstra, dim3((n_nodes + 63) / 64), dim3(64), 0, 0, n_nodes, k1, d_rp.get(), d_adj.get(),
+                       d_w.get(), d_nn.get(), d_nd.get(), d_of.get());
     MG_HIP(hipGetLastError());
     int of = 0;
-    MG_HIP(hipMemcpy(&of, d_of.p, sizeof(int), hipMemcpyDeviceToHost));
+    MG_HIP(hipMemcpy(&of, d_of.get(), sizeof(int), hipMemcpyDeviceToHost));
     if (of) {
         mg_set_error("knn_graph: a search needed more than %d live candidates (dense graph); not supported", KNN_MAXC);
         return MGADMM_ERR_UNSUPPORTED;
     }
-    MG_HIP(hipMemcpy(nn_out, d_nn.p, sizeof(int) * (size_t)n_nodes * k1, hipMemcpyDeviceToHost));
-    MG_HIP(hipMemcpy(nd_out, d_nd.p, sizeof(float) * (size_t)n_nodes * k1, hipMemcpyDeviceToHost));
+    MG_HIP(hipMemcpy(nn_out, d_nn.get(), sizeof(int) * (size_t)n_nodes * k1, hipMemcpyDeviceToHost));
+    MG_HIP(hipMemcpy(nd_out, d_nd.get(), sizeof(float) * (size_t)n_nodes * k1, hipMemcpyDeviceToHost));
     return MGADMM_OK;
 }
 
@@ -216,21 +206,23 @@ extern "C" int mgadmm_weight_tables(int32_t n_nodes, int32_t k1, const int64_t* 
     for (size_t i = 0; i < total; ++i)
         MG_REQUIRE(connect_list[i] >= -1 && connect_list[i] < n_nodes, "weight_tables: connect_list[%zu] = %lld out of range", i,
                    (long long)connect_list[i]);
-    DevBuf d_cl, d_dl, d_w, d_deg, d_mm;
-    MG_HIP(hipMalloc(&d_cl.p, sizeof(long long) * total));
-    MG_HIP(hipMalloc(&d_dl.p, sizeof(float) * total));
-    MG_HIP(hipMalloc(&d_w.p, sizeof(float) * total));
-    MG_HIP(hipMalloc(&d_deg.p, sizeof(float) * n_nodes));
-    MG_HIP(hipMalloc(&d_mm.p, sizeof(unsigned) * 2));
-    MG_HIP(hipMemcpy(d_cl.p, connect_list, sizeof(long long) * total, hipMemcpyHostToDevice));
-    MG_HIP(hipMemcpy(d_dl.p, dist_list, sizeof(float) * total, hipMemcpyHostToDevice));
+    DevBuf<long long> d_cl;
+    DevBuf<float> d_dl, d_w, d_deg;
+    DevBuf<unsigned> d_mm;
+    MG_BUF(d_cl.reserve(total));
+    MG_BUF(d_dl.reserve(total));
+    MG_BUF(d_w.reserve(total));
+    MG_BUF(d_deg.reserve(n_nodes));
+    MG_BUF(d_mm.reserve(2));
+    MG_HIP(hipMemcpy(d_cl.get(), connect_list, sizeof(long long) * total, hipMemcpyHostToDevice));
+    MG_HIP(hipMemcpy(d_dl.get(), dist_list, sizeof(float) * total, hipMemcpyHostToDevice));
     if (!(u_sigma > 0.0) || !(d_sigma > 0.0)) {
         const unsigned init[2] = {0xffffffffu, 0u};
-        MG_HIP(hipMemcpy(d_mm.p, init, sizeof(init), hipMemcpyHostToDevice));
+        MG_HIP(hipMemcpy(d_mm.get(), init, sizeof(init), hipMemcpyHostToDevice));
         hipLaunchKernelGGL(k_dist_range, dim3(std::min<long>(1024, (long)((total + 255) / 256))), dim3(256), 0, 0, (long)total,
-                           d_cl.as<long long>(), d_dl.as<float>(), d_mm.as<unsigned>(), d_mm.as<unsigned>() + 1);
+                           d_cl.get(), d_dl.get(), d_mm.get(), d_mm.get() + 1);
         unsigned mm[2];
-        MG_HIP(hipMemcpy(mm, d_mm.p, sizeof(mm), hipMemcpyDeviceToHost));
+        MG_HIP(hipMemcpy(mm, d_mm.get(), sizeof(mm), hipMemcpyDeviceToHost));
         MG_REQUIRE(mm[0] != 0xffffffffu, "weight_tables: no positive finite distance to derive the default sigma from");
         float fmin, fmax;
         memcpy(&fmin, &mm[0], 4);
@@ -243,19 +235,19 @@ extern "C" int mgadmm_weight_tables(int32_t n_nodes, int32_t k1, const int64_t* 
     const dim3 grid((n_nodes + 255) / 256), block(256);
     if (u_ew) {
         MG_REQUIRE(k1 >= 2, "weight_tables: undirected weights need at least one neighbour column");
-        hipLaunchKernelGGL(k_raw_weights, grid, block, 0, 0, n_nodes, k1, 1, (float)u_sigma, d_cl.as<long long>(), d_dl.as<float>(),
-                           d_w.as<float>(), d_deg.as<float>());
+        hipLaunchKernelGGL(k_raw_weights, grid, block, 0, 0, n_nodes, k1, 1, (float)u_sigma, d_cl.get(), d_dl.get(),
+                           d_w.get(), d_deg.get());
         if (regularized)
-            hipLaunchKernelGGL(k_norm_undirected, grid, block, 0, 0, n_nodes, k1, d_cl.as<long long>(), d_deg.as<float>(), d_w.as<float>());
+            hipLaunchKernelGGL(k_norm_undirected, grid, block, 0, 0, n_nodes, k1, d_cl.get(), d_deg.get(), d_w.get());
         MG_HIP(hipGetLastError());
-        MG_HIP(hipMemcpy(u_ew, d_w.p, sizeof(float) * (size_t)n_nodes * (k1 - 1), hipMemcpyDeviceToHost));
+        MG_HIP(hipMemcpy(u_ew, d_w.get(), sizeof(float) * (size_t)n_nodes * (k1 - 1), hipMemcpyDeviceToHost));
     }
     if (d_ew) {
-        hipLaunchKernelGGL(k_raw_weights, grid, block, 0, 0, n_nodes, k1, 0, (float)d_sigma, d_cl.as<long long>(), d_dl.as<float>(),
-                           d_w.as<float>(), d_deg.as<float>());
-        if (regularized) hipLaunchKernelGGL(k_norm_directed, grid, block, 0, 0, n_nodes, k1, d_deg.as<float>(), d_w.as<float>());
+        hipLaunchKernelGGL(k_raw_weights, grid, block, 0, 0, n_nodes, k1, 0, (float)d_sigma, d_cl.get(), d_dl.get(),
+                           d_w.get(), d_deg.get());
+        if (regularized) hipLaunchKernelGGL(k_norm_directed, grid, block, 0, 0, n_nodes, k1, d_deg.get(), d_w.get());
         MG_HIP(hipGetLastError());
-        MG_HIP(hipMemcpy(d_ew, d_w.p, sizeof(float) * total, hipMemcpyDeviceToHost));
+        MG_HIP(hipMemcpy(d_ew, d_w.get(), sizeof(float) * total, hipMemcpyDeviceToHost));
     }
     return MGADMM_OK;
 }

@@ -2,7 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "mgadmm.h"
@@ -32,13 +34,53 @@ void mg_set_error(const char* fmt, ...);
         if (rc_ != MGADMM_OK) return rc_;                                                      \
     } while (0)
 
+// a Buf's error code (dev_buf.h: what DevMem / PinnedMem returned, or BUF_TOO_LARGE) as the status MG_HIP gives a failed HIP call
+#define MG_BUF(x)                                                                              \
+    do {                                                                                       \
+        int e_ = (x);                                                                          \
+        if (e_ != 0) {                                                                         \
+            mg_set_error("%s:%d %s -> %s", __FILE__, __LINE__, #x, mg_buf_error(e_));         \
+            return MGADMM_ERR_HIP;                                                             \
+        }                                                                                      \
+    } while (0)
+
+#include "dev_buf.h"
 #include "host_csr.h"
+
+// ---- who owns device memory: Buf (dev_buf.h) over these two policies, and the two handles below.  Every owner releases in
+// its destructor; the destructors of the engines and mgadmm_graph_destroy select the device first.
+struct DevMem {
+    static int alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+    static int to_device(void* dst, const void* src, size_t bytes) { return (int)hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); }
+    static void release(void* p) { (void)hipFree(p); }
+};
+struct PinnedMem {
+    static int alloc(void** p, size_t bytes) { return (int)hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static int to_device(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
+    static void release(void* p) { (void)hipHostFree(p); }
+};
+template <class T> using DevBuf = Buf<T, DevMem>;
+template <class T> using PinnedBuf = Buf<T, PinnedMem>;
+inline const char* mg_buf_error(int e) { return e == BUF_TOO_LARGE ? "size overflows size_t" : hipGetErrorString((hipError_t)e); }
+
+// move-only owner of an event or a stream: created through put(), read as the plain handle
+template <class H, hipError_t (*Destroy)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(Handle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Handle& operator=(Handle&& o) noexcept { std::swap(h, o.h); return *this; }
+    ~Handle() { if (h) (void)Destroy(h); }
+    H* put() { return &h; }
+    operator H() const { return h; }
+};
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
 
 struct DevCsr {
     int n = 0, nnz = 0, max_row = 0, avg_row_ceil = 0;
-    int* rowptr = nullptr;
-    int* col = nullptr;
-    float* val = nullptr;
+    DevBuf<int> rowptr, col;
+    DevBuf<float> val;
 };
 
 // How a row-operator is evaluated by the row kernels (see k_rows in stream_kernels.h).
@@ -69,9 +111,9 @@ struct mgadmm_graph {
     std::vector<int> perm, iperm;  // perm[i] = API node at internal row i; iperm = inverse
     std::vector<int> cluster_starts;  // reorder = 2: first internal row of every cluster of the node order
     DevCsr Wu, Wd, WdT;            // internal node order, device
-    float* band_w = nullptr;       // device
-    double* ln_rowsum = nullptr;   // device, internal order: sum_j d_ew[i,j] (self coefficient of apply_op_Ln), built on first use
-    int* d_perm = nullptr;         // device (nullptr when identity)
+    DevBuf<float> band_w;          // device
+    DevBuf<double> ln_rowsum;      // device, internal order: sum_j d_ew[i,j] (self coefficient of apply_op_Ln), built on first use
+    DevBuf<int> d_perm;            // device (empty when identity)
     int max_row_all = 0;
 
     OpDesc op_lu() const;

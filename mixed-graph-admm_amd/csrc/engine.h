@@ -45,33 +45,32 @@ struct Engine : EngineBase {
     int T, N, Bmax, Bp_max;
     hipStream_t st = nullptr;
 
-    S* vec[V_COUNT] = {nullptr};
-    S* vec_pool = nullptr;
+    // Every block below belongs to its member (DevBuf / PinnedBuf, dev_buf.h), which knows its capacity: no size is kept beside it
+    S* vec[V_COUNT] = {nullptr};      // views into vec_pool
+    DevBuf<S> vec_pool;
     size_t vec_elems = 0;
-    S* partials = nullptr;
-    size_t partials_elems = 0;
+    DevBuf<S> partials;
     // CG scalars
-    S *d_rr = nullptr, *d_alpha = nullptr, *d_beta = nullptr, *d_alpha_hist = nullptr, *d_beta_hist = nullptr;
-    int *d_active = nullptr, *d_iters_tmp = nullptr, *d_nact = nullptr, *d_nonfinite = nullptr;
-    // history
-    double *d_ps = nullptr, *d_hist = nullptr, *d_dxps = nullptr, *d_dxpart = nullptr, *d_hist_ps = nullptr;
-    size_t hist_ps_elems = 0;
-    int* d_cg_iters = nullptr;
-    int max_admm_alloc = 0, max_cg_alloc = 0;
+    DevBuf<S> d_rr, d_alpha, d_beta, d_alpha_hist, d_beta_hist;
+    DevBuf<int> d_active, d_iters_tmp, d_nact, d_nonfinite;
+    // history (sized by the iteration limits: alloc_iter_dependent)
+    DevBuf<double> d_ps, d_hist, d_dxps, d_dxpart, d_hist_ps;
+    DevBuf<int> d_cg_iters;
     // pinned host
-    int* h_nact = nullptr;
-    double* h_row = nullptr;
-    int* h_flag = nullptr;
-    hipEvent_t ev_ring[LAG + 1] = {nullptr};
-    struct TileMetaDev { int R = 0; int GW = 0; int* tl_col = nullptr; float* tl_w = nullptr; int* halo = nullptr; int* h_rowptr = nullptr; int* h_col = nullptr; float* h_val = nullptr; };
+    PinnedBuf<int> h_nact;
+    PinnedBuf<double> h_row;
+    PinnedBuf<int> h_flag;
+    Event ev_ring[LAG + 1];
+    // R == 0: the tables are not valid (tile_meta sets R and GW after the last upload succeeded)
+    struct TileMetaDev { int R = 0; int GW = 0; DevBuf<int> tl_col; DevBuf<float> tl_w; DevBuf<int> halo, h_rowptr, h_col; DevBuf<float> h_val; };
     TileMetaDev tmeta[3];         // W_u, W_d, W_d^T metadata for the tile size in use
     // fused cLdr kernel (k_cldr): tile tables for the geometry in use; state 0 = not built yet, 1 = usable, -1 = the graph
     // does not fit its slot counts (hub rows): the two-pass form stays
     struct CldrDev {
         int state = 0, NT = 0;
         int gd = 8, gt = 12;      // W_d / W_d^T slots per row of the tables (streamplan::cldr_slots)
-        int *n0 = nullptr, *nC = nullptr, *rows = nullptr, *dcol = nullptr, *dcnt = nullptr, *tcol = nullptr, *tcnt = nullptr;
-        float *dw = nullptr, *tw = nullptr;
+        DevBuf<int> n0, nC, rows, dcol, dcnt, tcol, tcnt;
+        DevBuf<float> dw, tw;
     } cldr_dev;
     streamplan::Planner plan;     // geometry and kernel choice of the streaming path (stream_plan.h); its switches are read in init_workspace
     int cur_P = 0;                // partial rows written by the last row-kernel launch (k_rows or k_tile)
@@ -92,13 +91,13 @@ struct Engine : EngineBase {
     // kernels their expansion to a weight per batch column, [T*skip][bs_Bp] floats for the geometry of a solve of bs.B samples.
     // band_wb: non-null only while a solve with the table runs -- the fine-grained entry points and two_loops read the graph's own table
     bandsets::BandSets bs;
-    float* d_bs_exp = nullptr;
+    DevBuf<float> d_bs_exp;
     int bs_Bp = 0;
     const float* band_wb = nullptr;
     StreamKeyLog stream_keys;        // MGADMM_Q_STREAM_KEYS / _KEY0 + i: distinct k_rows / k_tile / k_cldr instances launched (stream_keys.h)
     // profiling
     bool prof_on = false;
-    std::vector<hipEvent_t> prof_ev;
+    std::vector<Event> prof_ev;
     std::vector<int> prof_tag;
     std::vector<double> prof_lb;   // algorithmic bytes of each timed launch
     std::vector<int> prof_ref;     // h_nact index that tells whether the launch did work (-1: unconditional launch)
@@ -112,21 +111,7 @@ struct Engine : EngineBase {
 
     explicit Engine(mgadmm_solver* s) : sv(s), g(s->g), p(s->p), T(s->g->T), N(s->g->N), Bmax(s->Bmax) {}
 
-    ~Engine() override {
-        (void)hipSetDevice(g->device);
-        auto fr = [](void* q) { if (q) (void)hipFree(q); };
-        fr(vec_pool); fr(partials); fr(d_rr); fr(d_alpha); fr(d_beta); fr(d_alpha_hist); fr(d_beta_hist);
-        fr(d_active); fr(d_iters_tmp); fr(d_nact); fr(d_nonfinite); fr(d_ps); fr(d_hist); fr(d_dxps);
-        fr(d_dxpart); fr(d_hist_ps); fr(d_cg_iters); fr(d_bs_exp);
-        for (auto& tmd : tmeta) { fr(tmd.tl_col); fr(tmd.tl_w); fr(tmd.halo); fr(tmd.h_rowptr); fr(tmd.h_col); fr(tmd.h_val); }
-        fr(cldr_dev.n0); fr(cldr_dev.nC); fr(cldr_dev.rows); fr(cldr_dev.dcol); fr(cldr_dev.dcnt); fr(cldr_dev.tcol); fr(cldr_dev.tcnt);
-        fr(cldr_dev.dw); fr(cldr_dev.tw);
-        if (h_nact) (void)hipHostFree(h_nact);
-        if (h_row) (void)hipHostFree(h_row);
-        if (h_flag) (void)hipHostFree(h_flag);
-        for (auto& e : ev_ring) if (e) (void)hipEventDestroy(e);
-        for (auto& e : prof_ev) (void)hipEventDestroy(e);
-    }
+    ~Engine() override { (void)hipSetDevice(g->device); }      // (in the body: it runs before the members release their blocks)
 
     // ---------------------------------------------------------------- geometry (the rules: stream_plan.h)
     streamplan::Facts plan_facts() const {
@@ -138,7 +123,7 @@ struct Engine : EngineBase {
     // which matrix a spatial operator applies (the graph hands out its three device tables; transpose_by_gather: Ldr^T reads W_d's)
     streamplan::Mat mat_of(const OpDesc& op) const {
         if (op.kind != OPK_SPATIAL) return op.kind == OPK_BAND ? streamplan::M_BAND : streamplan::M_NONE;
-        return op.rowptr == g->Wu.rowptr ? streamplan::M_WU : (op.rowptr == g->Wd.rowptr ? streamplan::M_WD : streamplan::M_WDT);
+        return op.rowptr == g->Wu.rowptr.get() ? streamplan::M_WU : (op.rowptr == g->Wd.rowptr.get() ? streamplan::M_WD : streamplan::M_WDT);
     }
 
     // host-side preprocessing of one CSR matrix for tile size R (see TileMeta in stream_kernels.h)
@@ -165,27 +150,18 @@ struct Engine : EngineBase {
                                 "entries %d, overflow entries %zu (%.2f %%)\n", which, R, TILE_GW, ntile, (double)hsum / ntile, TILE_HMAX,
                         hfull, A.nnz(), (size_t)tm.overflow(), 100.0 * tm.overflow() / std::max(1, A.nnz()));
             }
-            MG_HIP(hipStreamSynchronize(st));
-            auto fr = [](void* q) { if (q) (void)hipFree(q); };
-            fr(d.tl_col); fr(d.tl_w); fr(d.halo); fr(d.h_rowptr); fr(d.h_col); fr(d.h_val);
-            d = TileMetaDev();
-            const size_t nh = hcol.size();      // (with the padding)
-            MG_HIP(hipMalloc(&d.tl_col, tc.size() * sizeof(int)));
-            MG_HIP(hipMalloc(&d.tl_w, tw.size() * sizeof(float)));
-            MG_HIP(hipMalloc(&d.halo, halo.size() * sizeof(int)));
-            MG_HIP(hipMemcpy(d.halo, halo.data(), halo.size() * sizeof(int), hipMemcpyHostToDevice));
-            MG_HIP(hipMalloc(&d.h_rowptr, hr.size() * sizeof(int)));
-            MG_HIP(hipMalloc(&d.h_col, nh * sizeof(int)));
-            MG_HIP(hipMalloc(&d.h_val, nh * sizeof(float)));
-            MG_HIP(hipMemcpy(d.tl_col, tc.data(), tc.size() * sizeof(int), hipMemcpyHostToDevice));
-            MG_HIP(hipMemcpy(d.tl_w, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
-            MG_HIP(hipMemcpy(d.h_rowptr, hr.data(), hr.size() * sizeof(int), hipMemcpyHostToDevice));
-            MG_HIP(hipMemcpy(d.h_col, hcol.data(), nh * sizeof(int), hipMemcpyHostToDevice));
-            MG_HIP(hipMemcpy(d.h_val, hval.data(), nh * sizeof(float), hipMemcpyHostToDevice));
+            MG_HIP(hipStreamSynchronize(st));      // no launch reads the old tables any more
+            d.R = d.GW = 0;
+            MG_BUF(d.tl_col.upload(tc));
+            MG_BUF(d.tl_w.upload(tw));
+            MG_BUF(d.halo.upload(halo));
+            MG_BUF(d.h_rowptr.upload(hr));
+            MG_BUF(d.h_col.upload(hcol));       // (with the padding)
+            MG_BUF(d.h_val.upload(hval));
             d.R = R;
             d.GW = TILE_GW;
         }
-        out.tl_col = d.tl_col; out.tl_w = d.tl_w; out.halo = d.halo; out.h_rowptr = d.h_rowptr; out.h_col = d.h_col; out.h_val = d.h_val;
+        out.tl_col = d.tl_col.get(); out.tl_w = d.tl_w.get(); out.halo = d.halo.get(); out.h_rowptr = d.h_rowptr.get(); out.h_col = d.h_col.get(); out.h_val = d.h_val.get();
         return MGADMM_OK;
     }
 
@@ -222,14 +198,9 @@ struct Engine : EngineBase {
                     (double)tl.sumC2 / N, (double)tl.sumC1 / N);
         std::vector<int> nC((size_t)2 * tl.NT);
         for (int t = 0; t < tl.NT; ++t) { nC[2 * t] = tl.nC1[t]; nC[2 * t + 1] = tl.nC2[t]; }
-        auto up = [&](auto*& dst, const auto& v) -> bool {
-            typedef typename std::remove_reference<decltype(*dst)>::type E;
-            if (hipMalloc(&dst, std::max<size_t>(1, v.size()) * sizeof(E)) != hipSuccess) return false;
-            return v.empty() || hipMemcpy(dst, v.data(), v.size() * sizeof(E), hipMemcpyHostToDevice) == hipSuccess;
-        };
-        if (!(up(cldr_dev.n0, tl.n0) && up(cldr_dev.nC, nC) && up(cldr_dev.rows, tl.rows) && up(cldr_dev.dcol, tl.dcol) &&
-              up(cldr_dev.dw, tl.dw) && up(cldr_dev.dcnt, tl.dcnt) && up(cldr_dev.tcol, tl.tcol) && up(cldr_dev.tw, tl.tw) &&
-              up(cldr_dev.tcnt, tl.tcnt))) {
+        CldrDev& c = cldr_dev;
+        if (c.n0.upload(tl.n0) || c.nC.upload(nC) || c.rows.upload(tl.rows) || c.dcol.upload(tl.dcol) || c.dw.upload(tl.dw) ||
+            c.dcnt.upload(tl.dcnt) || c.tcol.upload(tl.tcol) || c.tw.upload(tl.tw) || c.tcnt.upload(tl.tcnt)) {
             (void)hipGetLastError();
             return;
         }
@@ -247,12 +218,13 @@ struct Engine : EngineBase {
     template <class G, int GD, int GT, template <typename, int> class E, template <typename, int> class SRC, class... A>
     int rows_cldr_gd(const Geom& q, const SRC<S, G::VECT>& src, const int* live, A... a) {
         const CldrGeom cg = plan.make_cldr_geom(q, cldr_dev.NT);
-        CldrMeta mm{cldr_dev.n0, cldr_dev.nC, cldr_dev.rows, cldr_dev.dcol, cldr_dev.dw, cldr_dev.dcnt, cldr_dev.tcol, cldr_dev.tw, cldr_dev.tcnt};
+        const CldrDev& c = cldr_dev;
+        CldrMeta mm{c.n0.get(), c.nC.get(), c.rows.get(), c.dcol.get(), c.dw.get(), c.dcnt.get(), c.tcol.get(), c.tw.get(), c.tcnt.get()};
         typedef E<S, G::VECT> Epi;
         auto fn = k_cldr<S, G::VECT, Epi, SRC<S, G::VECT>, G::NW, G::MA, G::MQ, G::MP, GD, GT, G::MINW>;
         MG_TRY(allow_dynamic_lds((const void*)fn, streamplan::CLDR_LDS_LIMIT));
         stream_keys.note(plan.key(plan.cldr_choice(GD, GT), Epi::ID, SRC<S, G::VECT>::FOLD));
-        hipLaunchKernelGGL(fn, dim3(cg.grid), dim3(G::NW * 64), cg.lds_bytes, st, cg, mm, src, Epi{a...}, partials, live);
+        hipLaunchKernelGGL(fn, dim3(cg.grid), dim3(G::NW * 64), cg.lds_bytes, st, cg, mm, src, Epi{a...}, partials.get(), live);
         cur_P = cg.P;
         return MGADMM_OK;
     }
@@ -285,7 +257,7 @@ struct Engine : EngineBase {
     template <template <typename, int> class E, class... A>
     int rows_cldr_fold(const Geom& q, const S* r, const S* p_old, S* p_new, S* x, const int* live, int tag, int passes, A... a) {
         const double bytes = pass_bytes(q, passes) + csr_bytes(g->op_ldr()) + csr_bytes(g->op_ldrt());
-        return rows_cldr_any<E, CldrSrcFold>(q, [&](auto gg) { return CldrSrcFold<S, decltype(gg)::VECT>{r, p_old, p_new, x, d_alpha, d_beta}; },
+        return rows_cldr_any<E, CldrSrcFold>(q, [&](auto gg) { return CldrSrcFold<S, decltype(gg)::VECT>{r, p_old, p_new, x, d_alpha.get(), d_beta.get()}; },
                                              live, tag, bytes, a...);
     }
 
@@ -294,13 +266,11 @@ struct Engine : EngineBase {
         int pmax = plan.make_tile_geom(q, tg) ? std::max(q.P, tg.P) : q.P;
         if (cldr_fits(q)) pmax = std::max(pmax, plan.make_cldr_geom(q, cldr_dev.NT).P);
         size_t need = (size_t)NRED_MAX * pmax * q.Bp;
-        if (need <= partials_elems) return MGADMM_OK;
-        MG_HIP(hipStreamSynchronize(st));
-        if (partials) MG_HIP(hipFree(partials));
-        partials = nullptr;
-        MG_HIP(hipMalloc(&partials, need * sizeof(S)));
-        ws_bytes += (int64_t)(need - partials_elems) * sizeof(S);
-        partials_elems = need;
+        const size_t had = partials.capacity();
+        if (need <= had) return MGADMM_OK;
+        MG_HIP(hipStreamSynchronize(st));      // no launch reads the old block any more
+        MG_BUF(partials.reserve(need));
+        ws_bytes += (int64_t)(need - had) * sizeof(S);
         return MGADMM_OK;
     }
 
@@ -314,23 +284,23 @@ struct Engine : EngineBase {
         // Bp for smaller batches never exceeds Bp_max rounded to 256
         Bp_max = std::max(Bp_max, ((Bmax + 63) / 64) * 64);
         vec_elems = (size_t)T * N * Bp_max;
-        MG_HIP(hipMalloc(&vec_pool, vec_elems * V_COUNT * sizeof(S)));
+        MG_BUF(vec_pool.reserve(vec_elems * V_COUNT));
         ws_bytes += (int64_t)vec_elems * V_COUNT * sizeof(S);
-        for (int i = 0; i < V_COUNT; ++i) vec[i] = vec_pool + vec_elems * i;
-        MG_HIP(hipMalloc(&d_rr, Bp_max * sizeof(S)));
-        MG_HIP(hipMalloc(&d_alpha, Bp_max * sizeof(S)));
-        MG_HIP(hipMalloc(&d_beta, Bp_max * sizeof(S)));
-        MG_HIP(hipMalloc(&d_active, Bp_max * sizeof(int)));
-        MG_HIP(hipMalloc(&d_iters_tmp, Bp_max * sizeof(int)));
-        MG_HIP(hipMalloc(&d_nonfinite, sizeof(int)));
-        MG_HIP(hipMemset(d_nonfinite, 0, sizeof(int)));
-        MG_HIP(hipMalloc(&d_ps, sizeof(double) * MGADMM_NMETRIC * Bp_max));
+        for (int i = 0; i < V_COUNT; ++i) vec[i] = vec_pool.get() + vec_elems * i;
+        MG_BUF(d_rr.reserve(Bp_max));
+        MG_BUF(d_alpha.reserve(Bp_max));
+        MG_BUF(d_beta.reserve(Bp_max));
+        MG_BUF(d_active.reserve(Bp_max));
+        MG_BUF(d_iters_tmp.reserve(Bp_max));
+        MG_BUF(d_nonfinite.upload({0}));
+        MG_BUF(d_ps.reserve((size_t)MGADMM_NMETRIC * Bp_max));
         const int nbk = (N + 63) / 64;
-        MG_HIP(hipMalloc(&d_dxpart, sizeof(double) * T * nbk));
-        MG_HIP(hipHostMalloc(&h_row, sizeof(double) * (MGADMM_NMETRIC + 1)));
-        MG_HIP(hipHostMalloc(&h_flag, sizeof(int) * 4));
-        for (auto& e : ev_ring) MG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        return alloc_iter_dependent();
+        MG_BUF(d_dxpart.reserve((size_t)T * nbk));
+        MG_BUF(h_row.reserve(MGADMM_NMETRIC + 1));
+        MG_BUF(h_flag.reserve(4));
+        for (auto& e : ev_ring) MG_HIP(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
+        MG_BUF(alloc_iter_dependent((size_t)p.max_admm_iter));
+        return MGADMM_OK;
     }
     int init() override {
         MG_TRY(init_workspace());
@@ -345,28 +315,22 @@ struct Engine : EngineBase {
     solvegate::SetState set_state() const { return {wt.sp_B, sg_B, wt.sch_rows, wt.sch_B, ad_on}; }
     static int refused(const solvegate::Result& r) { if (r.rc != MGADMM_OK) mg_set_error("%s", r.msg.c_str()); return r.rc; }
 
-    int alloc_iter_dependent() {
-        auto fr = [](void* q) { if (q) (void)hipFree(q); };
-        if (p.max_cg_iter > max_cg_alloc) {
-            fr(d_nact); fr(d_alpha_hist); fr(d_beta_hist);
-            if (h_nact) (void)hipHostFree(h_nact);
-            d_nact = nullptr; d_alpha_hist = d_beta_hist = nullptr; h_nact = nullptr;
-            max_cg_alloc = p.max_cg_iter;
-            MG_HIP(hipMalloc(&d_nact, sizeof(int) * max_cg_alloc));
-            MG_HIP(hipMalloc(&d_alpha_hist, sizeof(S) * 3 * (size_t)max_cg_alloc * Bp_max));
-            MG_HIP(hipMalloc(&d_beta_hist, sizeof(S) * 3 * (size_t)max_cg_alloc * Bp_max));
-            MG_HIP(hipHostMalloc(&h_nact, sizeof(int) * (NACT_LOG + (size_t)max_cg_alloc)));
+    // The buffers sized by the iteration limits: max_cg_iter of `p`, and `rows` ADMM iterations of history (max_admm_iter; two_loops:
+    // outer x inner).  Called by set_params and at the head of every entry point that reads them, where it compares seven
+    // capacities once they suffice: whatever an earlier call left, no launch sees a buffer smaller than `p` demands.  A buffer
+    // grows on its own (Buf::reserve: a failure leaves it as it was); the error code of the first failure is returned
+    int alloc_iter_dependent(size_t rows) {
+        const size_t K = (size_t)p.max_cg_iter;
+        if (int e = d_nact.reserve(K)) return e;
+        if (int e = d_alpha_hist.reserve(3 * K * Bp_max)) return e;
+        if (int e = d_beta_hist.reserve(3 * K * Bp_max)) return e;
+        if (h_nact.capacity() < NACT_LOG + K) {
+            if (int e = h_nact.reserve(NACT_LOG + K)) return e;
             nact_cur = 0;
         }
-        if (p.max_admm_iter > max_admm_alloc) {
-            fr(d_hist); fr(d_dxps); fr(d_cg_iters);
-            d_hist = d_dxps = nullptr; d_cg_iters = nullptr;
-            max_admm_alloc = p.max_admm_iter;
-            MG_HIP(hipMalloc(&d_hist, sizeof(double) * (size_t)max_admm_alloc * MGADMM_NMETRIC));
-            MG_HIP(hipMalloc(&d_dxps, sizeof(double) * (size_t)max_admm_alloc * T));
-            MG_HIP(hipMalloc(&d_cg_iters, sizeof(int) * (size_t)max_admm_alloc * 3 * Bp_max));
-        }
-        return MGADMM_OK;
+        if (int e = d_hist.reserve(rows * MGADMM_NMETRIC)) return e;
+        if (int e = d_dxps.reserve(rows * T)) return e;
+        return d_cg_iters.reserve(rows * 3 * Bp_max);
     }
 
     int set_params(const mgadmm_params& np) override {
@@ -382,7 +346,8 @@ struct Engine : EngineBase {
         p = np;
         sv->p = np;
         MG_HIP(hipSetDevice(g->device));
-        return alloc_iter_dependent();
+        MG_BUF(alloc_iter_dependent((size_t)p.max_admm_iter));
+        return MGADMM_OK;
     }
 
     // ---------------------------------------------------------------- per-sample and per-iteration ADMM weights
@@ -454,18 +419,14 @@ struct Engine : EngineBase {
         MG_HIP(hipSetDevice(g->device));
         MG_TRY(refused(bs.set(g->mode == MGADMM_TEMPORAL_BAND, T, g->skip, n_sets, band_w, set_of_sample, B, Bmax)));
         MG_HIP(hipDeviceSynchronize());
-        if (d_bs_exp) (void)hipFree(d_bs_exp);
-        d_bs_exp = nullptr;
+        d_bs_exp.reset();
         bs_Bp = 0;
         if (bs.B == 0) return MGADMM_OK;
         std::vector<float> exp;
         const int Bp = plan.make_geom(bs.B).Bp;
         bs.expand(Bp, exp);
-        if (hipMalloc(&d_bs_exp, sizeof(float) * exp.size()) != hipSuccess ||
-            hipMemcpy(d_bs_exp, exp.data(), sizeof(float) * exp.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        if (d_bs_exp.upload(exp) != 0) {
             (void)hipGetLastError();
-            if (d_bs_exp) (void)hipFree(d_bs_exp);
-            d_bs_exp = nullptr;
             bs.clear();
             mg_set_error("set_sample_bands: upload of the expanded table failed");
             return MGADMM_ERR_HIP;
@@ -522,7 +483,7 @@ struct Engine : EngineBase {
         MG_HIP(hipSetDevice(g->device));
         if (prof_ev.empty()) {
             prof_ev.resize(2 * PROF_POOL);
-            for (auto& e : prof_ev) MG_HIP(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));   // timing only: no system-scope cache flush per record
+            for (auto& e : prof_ev) MG_HIP(hipEventCreateWithFlags(e.put(), hipEventDisableSystemFence));   // timing only: no system-scope cache flush per record
             prof_tag.resize(PROF_POOL);
             prof_lb.resize(PROF_POOL);
             prof_ref.resize(PROF_POOL);
@@ -548,7 +509,7 @@ struct Engine : EngineBase {
             // active-sample counts the host copies back for its own convergence check (h_nact), not guessed from
             // the duration: such a launch is left out of BOTH the bytes and the time, so the reported rates are
             // those of launches that did the work.
-            if (prof_ref[i] >= 0 && h_nact[prof_ref[i]] == 0) {
+            if (prof_ref[i] >= 0 && h_nact.get()[prof_ref[i]] == 0) {
                 prof_noop++;
                 continue;
             }
@@ -615,7 +576,7 @@ struct Engine : EngineBase {
         MG_TRY(allow_dynamic_lds((const void*)fn, 80 * 1024));
         stream_keys.note(plan.key(c, Epi::ID, false));
         hipLaunchKernelGGL(fn, dim3(tg.grid), dim3(256), tg.lds_bytes, st, tg, op, tmv.tl_col, tmv.tl_w, tmv.halo, tmv.h_rowptr,
-                           tmv.h_col, tmv.h_val, in, epi, partials, live, TileSrcPlain<S, VEC>());
+                           tmv.h_col, tmv.h_val, in, epi, partials.get(), live, TileSrcPlain<S, VEC>());
         return MGADMM_OK;
     }
 
@@ -637,7 +598,7 @@ struct Engine : EngineBase {
         MG_TRY(allow_dynamic_lds((const void*)fn, 80 * 1024));
         stream_keys.note(plan.key(c, Epi::ID, true));
         hipLaunchKernelGGL(fn, dim3(tg.grid), dim3(256), tg.lds_bytes, st, tg, op, tmv.tl_col, tmv.tl_w, tmv.halo, tmv.h_rowptr,
-                           tmv.h_col, tmv.h_val, r, Epi{a...}, partials, live, Src{p_old, p_new, x, d_alpha, d_beta});
+                           tmv.h_col, tmv.h_val, r, Epi{a...}, partials.get(), live, Src{p_old, p_new, x, d_alpha.get(), d_beta.get()});
         cur_P = tg.P;
         if (timed) prof_close();
         MG_HIP(hipGetLastError());
@@ -666,7 +627,7 @@ struct Engine : EngineBase {
         } else {
             stream_keys.note(plan.key(c, Epi::ID, false));
             hipLaunchKernelGGL((k_rows<S, VEC, Epi, GW>), dim3(q.grid), dim3(256), 0, st, q, op, op.rowptr, op.col, op.val,
-                               op.band_w, in, epi, partials, live);
+                               op.band_w, in, epi, partials.get(), live);
             cur_P = q.P;
         }
         if (timed) prof_close();
@@ -698,7 +659,7 @@ struct Engine : EngineBase {
     template <int NRED, class Fin>
     int reduce(const Geom& q, const Fin& fin, const int* live) {
         prof_open(3, 0);
-        hipLaunchKernelGGL((k_reduce<S, NRED, Fin>), dim3(q.Bp / 64), dim3(1024), 0, st, partials, cur_P, q.Bp, fin, live);
+        hipLaunchKernelGGL((k_reduce<S, NRED, Fin>), dim3(q.Bp / 64), dim3(1024), 0, st, partials.get(), cur_P, q.Bp, fin, live);
         MG_HIP(hipGetLastError());
         return MGADMM_OK;
     }
@@ -715,14 +676,14 @@ struct Engine : EngineBase {
     int pack(const Geom& q, const void* src, int Ts, S* dst) {
         dim3 grid((N + 63) / 64, T, q.Bp / 64);
         prof_open(3, 0);
-        hipLaunchKernelGGL((k_pack<S>), grid, dim3(256), 0, st, T, Ts, N, q.B, q.Bp, g->d_perm, (const S*)src, dst);
+        hipLaunchKernelGGL((k_pack<S>), grid, dim3(256), 0, st, T, Ts, N, q.B, q.Bp, g->d_perm.get(), (const S*)src, dst);
         MG_HIP(hipGetLastError());
         return MGADMM_OK;
     }
     int unpack(const Geom& q, const S* src, void* dst) {
         dim3 grid((N + 63) / 64, T, q.Bp / 64);
         prof_open(3, 0);
-        hipLaunchKernelGGL((k_unpack<S>), grid, dim3(256), 0, st, T, N, q.B, q.Bp, g->d_perm, src, (S*)dst);
+        hipLaunchKernelGGL((k_unpack<S>), grid, dim3(256), 0, st, T, N, q.B, q.Bp, g->d_perm.get(), src, (S*)dst);
         MG_HIP(hipGetLastError());
         return MGADMM_OK;
     }
@@ -764,15 +725,14 @@ struct Engine : EngineBase {
                 for (int e = g->hWd.rowptr[i]; e < g->hWd.rowptr[i + 1]; ++e) a += (double)g->hWd.val[e];
                 rs[r] = a;
             }
-            MG_HIP(hipMalloc(&g->ln_rowsum, sizeof(double) * N));
-            MG_HIP(hipMemcpy(g->ln_rowsum, rs.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+            MG_BUF(g->ln_rowsum.upload(rs));      // (a failed copy leaves it empty: the next call builds it again)
         }
         OpDesc child = g->op_ldr();
-        child.self_w = g->ln_rowsum;
+        child.self_w = g->ln_rowsum.get();
         OpDesc father = g->op_ldrt();
         father.self_mode = SELF_LN_FATHER;
         father.q1 = 0;
-        father.self_w = g->ln_rowsum;
+        father.self_w = g->ln_rowsum.get();
         MG_TRY(rows<EpiStore>(q, child, in, nullptr, 2, 2, vec[V_Q]));
         return rows<EpiAddTo>(q, father, in, nullptr, 2, 3, (const S*)vec[V_Q], out);
     }
@@ -796,16 +756,16 @@ struct Engine : EngineBase {
     int cg_internal(const Geom& q, const LhsDef& d, const S* rhs, const S* x0, const S* mask, S* xout, int* iters_dev,
                     bool record, int* n_iter_launched = nullptr) {
         CgScalars<S> c;
-        c.rr = d_rr; c.alpha = d_alpha; c.beta = d_beta; c.active = d_active; c.iters = iters_dev; c.n_active = d_nact;
-        c.alpha_hist = record ? d_alpha_hist : nullptr;
-        c.beta_hist = record ? d_beta_hist : nullptr;
-        c.nonfinite = d_nonfinite;
+        c.rr = d_rr.get(); c.alpha = d_alpha.get(); c.beta = d_beta.get(); c.active = d_active.get(); c.iters = iters_dev; c.n_active = d_nact.get();
+        c.alpha_hist = record ? d_alpha_hist.get() : nullptr;
+        c.beta_hist = record ? d_beta_hist.get() : nullptr;
+        c.nonfinite = d_nonfinite.get();
         const int K = p.max_cg_iter;
         const int batch_max = p.cg_convergence == MGADMM_CG_BATCH_MAX ? 1 : 0;
-        MG_HIP(hipMemsetAsync(d_nact, 0, sizeof(int) * K, st));
+        MG_HIP(hipMemsetAsync(d_nact.get(), 0, sizeof(int) * K, st));
         if (record) {
-            MG_TRY(fill(d_alpha_hist, (size_t)K * q.Bp, (S)NAN));
-            MG_TRY(fill(d_beta_hist, (size_t)K * q.Bp, (S)NAN));
+            MG_TRY(fill(d_alpha_hist.get(), (size_t)K * q.Bp, (S)NAN));
+            MG_TRY(fill(d_beta_hist.get(), (size_t)K * q.Bp, (S)NAN));
         }
         S *r = vec[V_R], *pp = vec[V_P], *Ap = vec[V_AP];
         // r = rhs - A x0 ; p = r ; x = x0
@@ -838,7 +798,7 @@ struct Engine : EngineBase {
         S* pbuf[2] = {pp, vec[V_Q]};          // V_Q is free: the fused kernel keeps q = Ldr p on chip
         int k = 0;
         for (; k < K; ++k) {
-            const int* live = k == 0 ? nullptr : d_nact + (k - 1);
+            const int* live = k == 0 ? nullptr : d_nact.get() + (k - 1);
             prof_cur_ref = (k == 0 || nact_locked) ? -1 : base + k - 1;
             if (fold2) {
                 // 1 SpMM application (8 B/element) + the absorbed vector update (20 B/element) per launch
@@ -857,17 +817,17 @@ struct Engine : EngineBase {
                 // last slices of Ap (still in the Infinity Cache), and the kernel after it starts with the first slices of r
                 Geom qr = q;
                 qr.rev = plan.sw.sweep_rev;
-                MG_TRY(rows<EpiCgUpdate>(qr, op_none(), Ap, live, 1, 3, (const S*)d_alpha, r));
+                MG_TRY(rows<EpiCgUpdate>(qr, op_none(), Ap, live, 1, 3, (const S*)d_alpha.get(), r));
             }
             MG_TRY((reduce<1>(q, FinCgBeta<S>{c, k, q.Bp, p.cg_tol, batch_max}, live)));
             if (!fold)
-                MG_TRY(rows<EpiPUpdate>(q, op_none(), r, live, 1, 5, (const S*)d_alpha, (const S*)d_beta, xout, pp));   // x += alpha p, p = r + beta p
+                MG_TRY(rows<EpiPUpdate>(q, op_none(), r, live, 1, 5, (const S*)d_alpha.get(), (const S*)d_beta.get(), xout, pp));   // x += alpha p, p = r + beta p
             prof_cur_ref = -1;
-            MG_HIP(hipMemcpyAsync(h_nact + base + k, d_nact + k, sizeof(int), hipMemcpyDeviceToHost, st));
+            MG_HIP(hipMemcpyAsync(h_nact.get() + base + k, d_nact.get() + k, sizeof(int), hipMemcpyDeviceToHost, st));
             MG_HIP(hipEventRecord(ev_ring[k % (LAG + 1)], st));
             if (k >= LAG) {
                 MG_HIP(hipEventSynchronize(ev_ring[(k - LAG) % (LAG + 1)]));
-                if (h_nact[base + k - LAG] == 0) { ++k; break; }
+                if (h_nact.get()[base + k - LAG] == 0) { ++k; break; }
             }
         }
         if (fold) {
@@ -877,12 +837,12 @@ struct Engine : EngineBase {
             const int launched = std::min(k, K);
             int kl = launched - 1;
             for (int j = 0; j < launched; ++j)
-                if (h_nact[base + j] == 0) { kl = j; break; }
-            MG_TRY(rows<EpiXFinal>(q, op_none(), pbuf[(kl + 1) & 1], nullptr, 1, 3, (const S*)d_alpha, xout));
+                if (h_nact.get()[base + j] == 0) { kl = j; break; }
+            MG_TRY(rows<EpiXFinal>(q, op_none(), pbuf[(kl + 1) & 1], nullptr, 1, 3, (const S*)d_alpha.get(), xout));
         }
         if (!nact_locked) nact_cur += std::min(k, K);
         if (batch_max) {          // one iteration count for the whole batch: the first iteration after which no sample was above the tolerance
-            hipLaunchKernelGGL(k_cg_batchmax_iters, dim3((q.B + 255) / 256), dim3(256), 0, st, (const int*)d_nact, std::min(k, K), iters_dev, q.B);
+            hipLaunchKernelGGL(k_cg_batchmax_iters, dim3((q.B + 255) / 256), dim3(256), 0, st, (const int*)d_nact.get(), std::min(k, K), iters_dev, q.B);
             MG_HIP(hipGetLastError());
         }
         if (n_iter_launched) *n_iter_launched = k;
@@ -958,9 +918,9 @@ struct Engine : EngineBase {
     int interp_internal(const Geom& q, const S* y, const S* mask, int mask_f32, S* x) {
         dim3 grid((N + 3) / 4, q.Bp / 64);
         if (mask_f32 && sizeof(S) == 8)
-            hipLaunchKernelGGL((k_initial_interp<S, true>), grid, dim3(256), 0, st, T, N, q.Bp, q.B, y, mask, x, d_nonfinite);
+            hipLaunchKernelGGL((k_initial_interp<S, true>), grid, dim3(256), 0, st, T, N, q.Bp, q.B, y, mask, x, d_nonfinite.get());
         else
-            hipLaunchKernelGGL((k_initial_interp<S, false>), grid, dim3(256), 0, st, T, N, q.Bp, q.B, y, mask, x, d_nonfinite);
+            hipLaunchKernelGGL((k_initial_interp<S, false>), grid, dim3(256), 0, st, T, N, q.Bp, q.B, y, mask, x, d_nonfinite.get());
         MG_HIP(hipGetLastError());
         return MGADMM_OK;
     }
@@ -999,13 +959,14 @@ struct Engine : EngineBase {
     int cg(int which, const void* rhs, const void* x0, const void* mask, void* x, int32_t* iters, double* alpha,
            double* beta, int B, hipStream_t s) override {
         MG_TRY(check_B(B, "cg"));
+        MG_BUF(alloc_iter_dependent((size_t)p.max_admm_iter));      // (nothing to do unless an earlier set_params failed to allocate)
         MG_REQUIRE(rhs && x && iters, "cg: null pointer");
         MG_REQUIRE(which >= 0 && which <= 2, "cg: bad operator id %d", which);
         MG_REQUIRE(!(which == MGADMM_LHS_ZD && p.ablation == MGADMM_ABL_DGLR), "cg: LHS_zd is undefined for ablation 'DGLR'");
         st = s;
         Geom q = plan.make_geom(B);
         MG_TRY(ensure_partials(q));
-        MG_HIP(hipMemsetAsync(d_nonfinite, 0, sizeof(int), st));
+        MG_HIP(hipMemsetAsync(d_nonfinite.get(), 0, sizeof(int), st));
         MG_TRY(pack(q, rhs, T, vec[V_RHS]));
         if (x0) MG_TRY(pack(q, x0, T, vec[V_IO0]));
         else MG_HIP(hipMemsetAsync(vec[V_IO0], 0, velems(q) * sizeof(S), st));
@@ -1014,15 +975,15 @@ struct Engine : EngineBase {
             MG_TRY(pack(q, mask, T, vec[V_MASK]));
             m = vec[V_MASK];
         }
-        MG_TRY(cg_internal(q, lhs_def(which), vec[V_RHS], vec[V_IO0], m, vec[V_IO1], d_iters_tmp, true));
+        MG_TRY(cg_internal(q, lhs_def(which), vec[V_RHS], vec[V_IO0], m, vec[V_IO1], d_iters_tmp.get(), true));
         MG_TRY(unpack(q, vec[V_IO1], x));
-        MG_HIP(hipMemcpyAsync(iters, d_iters_tmp, sizeof(int) * B, hipMemcpyDeviceToHost, st));
-        MG_HIP(hipMemcpyAsync(h_flag, d_nonfinite, sizeof(int), hipMemcpyDeviceToHost, st));
+        MG_HIP(hipMemcpyAsync(iters, d_iters_tmp.get(), sizeof(int) * B, hipMemcpyDeviceToHost, st));
+        MG_HIP(hipMemcpyAsync(h_flag.get(), d_nonfinite.get(), sizeof(int), hipMemcpyDeviceToHost, st));
         MG_HIP(hipStreamSynchronize(st));
         const size_t K = p.max_cg_iter;
-        if (alpha) MG_TRY(fetch_hist(d_alpha_hist, K * q.Bp, alpha, B, q.Bp, K));
-        if (beta) MG_TRY(fetch_hist(d_beta_hist, K * q.Bp, beta, B, q.Bp, K));
-        if (h_flag[0]) {
+        if (alpha) MG_TRY(fetch_hist(d_alpha_hist.get(), K * q.Bp, alpha, B, q.Bp, K));
+        if (beta) MG_TRY(fetch_hist(d_beta_hist.get(), K * q.Bp, beta, B, q.Bp, K));
+        if (h_flag.get()[0]) {
             mg_set_error("cg: non-finite residual met");
             return MGADMM_ERR_NONFINITE;
         }
@@ -1040,35 +1001,25 @@ struct Engine : EngineBase {
         return MGADMM_OK;
     }
 
-    // device buffer that grows on demand; a failed allocation leaves it empty
-    template <class E>
-    int grow(E*& buf, size_t& elems, size_t need) {
-        if (need <= elems) return MGADMM_OK;
-        if (buf) MG_HIP(hipFree(buf));
-        buf = nullptr;
-        elems = 0;
-        MG_HIP(hipMalloc(&buf, need * sizeof(E)));
-        elems = need;
-        return MGADMM_OK;
-    }
     // per-sample metric history of a solve, when the caller asks for it
     int ensure_hist_ps(const mgadmm_history* hist, int B) {
         if (!hist || !hist->metrics_per_sample) return MGADMM_OK;
-        return grow(d_hist_ps, hist_ps_elems, (size_t)p.max_admm_iter * MGADMM_NMETRIC * B);
+        MG_BUF(d_hist_ps.reserve((size_t)p.max_admm_iter * MGADMM_NMETRIC * B));
+        return MGADMM_OK;
     }
     // The host's stop test after iteration `it` (ADMM.py:645-646): copies the metric row and the non-finite flag, waits for
     // the stream, and sets *stop when the loop ends here: both residual maxima are below admm_tol, or a NaN / Inf was met
     // (*rc_final = MGADMM_ERR_NONFINITE)
     int host_stop_test(int it, bool has_phi, bool has_zd, bool* stop, int* rc_final) {
-        MG_HIP(hipMemcpyAsync(h_row, d_hist + (size_t)it * MGADMM_NMETRIC, sizeof(double) * MGADMM_NMETRIC, hipMemcpyDeviceToHost, st));
-        MG_HIP(hipMemcpyAsync(h_flag, d_nonfinite, sizeof(int), hipMemcpyDeviceToHost, st));
+        MG_HIP(hipMemcpyAsync(h_row.get(), d_hist.get() + (size_t)it * MGADMM_NMETRIC, sizeof(double) * MGADMM_NMETRIC, hipMemcpyDeviceToHost, st));
+        MG_HIP(hipMemcpyAsync(h_flag.get(), d_nonfinite.get(), sizeof(int), hipMemcpyDeviceToHost, st));
         MG_HIP(hipStreamSynchronize(st));
-        bool finite = h_flag[0] == 0;
-        for (int k = 0; k < MGADMM_NMETRIC; ++k) finite = finite && std::isfinite(h_row[k]);
+        bool finite = h_flag.get()[0] == 0;
+        for (int k = 0; k < MGADMM_NMETRIC; ++k) finite = finite && std::isfinite(h_row.get()[k]);
         if (!finite) { *rc_final = MGADMM_ERR_NONFINITE; *stop = true; return MGADMM_OK; }
-        double pri = h_row[MGADMM_M_PRI_ZU], dual = h_row[MGADMM_M_DUAL_ZU];
-        if (has_phi) { pri = std::max(pri, h_row[MGADMM_M_PRI_PHI]); dual = std::max(dual, h_row[MGADMM_M_DUAL_PHI]); }
-        if (has_zd) { pri = std::max(pri, h_row[MGADMM_M_PRI_ZD]); dual = std::max(dual, h_row[MGADMM_M_DUAL_ZD]); }
+        double pri = h_row.get()[MGADMM_M_PRI_ZU], dual = h_row.get()[MGADMM_M_DUAL_ZU];
+        if (has_phi) { pri = std::max(pri, h_row.get()[MGADMM_M_PRI_PHI]); dual = std::max(dual, h_row.get()[MGADMM_M_DUAL_PHI]); }
+        if (has_zd) { pri = std::max(pri, h_row.get()[MGADMM_M_PRI_ZD]); dual = std::max(dual, h_row.get()[MGADMM_M_DUAL_ZD]); }
         *stop = pri < p.admm_tol && dual < p.admm_tol;
         return MGADMM_OK;
     }
@@ -1138,6 +1089,7 @@ struct Engine : EngineBase {
     int solve(const void* y, const void* mask, int mask_f32, int B, const void* x0, const mgadmm_state* state_in, void* x_out,
               const mgadmm_state* state_out, mgadmm_history* hist, hipStream_t s) override {
         MG_TRY(check_B(B, "solve"));
+        MG_BUF(alloc_iter_dependent((size_t)p.max_admm_iter));      // (as in cg)
         MG_REQUIRE(y && x_out, "solve: null pointer");
         if (state_in) MG_TRY(check_state_in(x0, state_in));
         st = s;
@@ -1150,8 +1102,8 @@ struct Engine : EngineBase {
         // a band table: the Ldr / Ldr^T of this solve read a weight per batch column (op_ldr, op_ldrt) until it returns
         struct BandScope { const float*& wb; ~BandScope() { wb = nullptr; } } band_scope{band_wb};
         if (bs.B > 0) {
-            MG_REQUIRE(d_bs_exp && bs_Bp == q.Bp, "solve: the sample_bands table was expanded for %d columns, the solve has %d", bs_Bp, q.Bp);
-            band_wb = d_bs_exp;
+            MG_REQUIRE(d_bs_exp.get() && bs_Bp == q.Bp, "solve: the sample_bands table was expanded for %d columns, the solve has %d", bs_Bp, q.Bp);
+            band_wb = d_bs_exp.get();
         }
         MG_TRY(ensure_partials(q));
         const size_t ne = velems(q);
@@ -1159,9 +1111,9 @@ struct Engine : EngineBase {
         const int max_it = p.max_admm_iter;
         const bool record = p.record_cg_coeffs && hist && hist->cg_alpha && hist->cg_beta;
         MG_TRY(ensure_hist_ps(hist, B));
-        MG_HIP(hipMemsetAsync(d_nonfinite, 0, sizeof(int), st));
-        MG_HIP(hipMemsetAsync(d_ps, 0, sizeof(double) * MGADMM_NMETRIC * q.Bp, st));
-        MG_HIP(hipMemsetAsync(d_cg_iters, 0, sizeof(int) * (size_t)max_it * 3 * q.Bp, st));
+        MG_HIP(hipMemsetAsync(d_nonfinite.get(), 0, sizeof(int), st));
+        MG_HIP(hipMemsetAsync(d_ps.get(), 0, sizeof(double) * MGADMM_NMETRIC * q.Bp, st));
+        MG_HIP(hipMemsetAsync(d_cg_iters.get(), 0, sizeof(int) * (size_t)max_it * 3 * q.Bp, st));
 
         Bufs b;
         const S* m = nullptr;
@@ -1197,24 +1149,24 @@ struct Engine : EngineBase {
             double w[6];
             ldsparam::row_weights(wsrc, it, wt.sch_row0, w);
             const S rho = (S)w[0];
-            MG_TRY(admm_step(q, w, b, d_cg_iters + (size_t)it * 3 * q.Bp, m, record, hist, it));
-            MG_TRY((reduce<6>(q, FinMetrics<6>{d_ps, q.Bp, {MGADMM_M_XSHIFT, MGADMM_M_PRI_ZU, MGADMM_M_DUAL_ZU, has_zd ? MGADMM_M_PRI_ZD : -1,
+            MG_TRY(admm_step(q, w, b, d_cg_iters.get() + (size_t)it * 3 * q.Bp, m, record, hist, it));
+            MG_TRY((reduce<6>(q, FinMetrics<6>{d_ps.get(), q.Bp, {MGADMM_M_XSHIFT, MGADMM_M_PRI_ZU, MGADMM_M_DUAL_ZU, has_zd ? MGADMM_M_PRI_ZD : -1,
                                                        has_zd ? MGADMM_M_DUAL_ZD : -1, MGADMM_M_RECOVER}}, nullptr)));
             // ---- phi prox, gamma update, Ldr-based residuals and regularisers (ADMM.py:600-606, 627-637)
             MG_TRY(rows<EpiPhi>(q, op_ldr(), vec[b.xn], nullptr, 2, has_phi ? 5 : 1, (const S*)vec[b.phc], vec[b.phn], vec[V_GAM],
                                 rho, (S)(w[4] / w[0]), has_phi ? 1 : 0));
-            MG_TRY((reduce<4>(q, FinMetrics<4>{d_ps, q.Bp, {has_phi ? MGADMM_M_PRI_PHI : -1, has_phi ? MGADMM_M_DUAL_PHI : -1,
+            MG_TRY((reduce<4>(q, FinMetrics<4>{d_ps.get(), q.Bp, {has_phi ? MGADMM_M_PRI_PHI : -1, has_phi ? MGADMM_M_DUAL_PHI : -1,
                                                        has_phi ? MGADMM_M_DGTV : -1, has_zd ? MGADMM_M_DGLR : -1}}, nullptr)));
             MG_TRY(rows<EpiDot>(q, g->op_lu(), vec[b.xn], nullptr, 2, 1));
-            MG_TRY((reduce<1>(q, FinMetrics<1>{d_ps, q.Bp, {MGADMM_M_GLR}}, nullptr)));
+            MG_TRY((reduce<1>(q, FinMetrics<1>{d_ps.get(), q.Bp, {MGADMM_M_GLR}}, nullptr)));
             const int nbk = (N + 63) / 64;
             hipLaunchKernelGGL((k_dxps<S>), dim3(T * nbk), dim3(256), 0, st, T, N, q.Bp, B, nbk, (const S*)vec[b.xn],
-                               (const S*)vec[b.xc], d_dxpart);
-            hipLaunchKernelGGL(k_dxps_final, dim3((T + 63) / 64), dim3(64), 0, st, T, nbk, (const double*)d_dxpart,
-                               d_dxps + (size_t)it * T);
-            hipLaunchKernelGGL(k_batch_metrics, dim3(MGADMM_NMETRIC), dim3(256), 0, st, (const double*)d_ps, q.Bp, B,
-                               d_hist + (size_t)it * MGADMM_NMETRIC,
-                               (hist && hist->metrics_per_sample) ? d_hist_ps + (size_t)it * MGADMM_NMETRIC * B : nullptr);
+                               (const S*)vec[b.xc], d_dxpart.get());
+            hipLaunchKernelGGL(k_dxps_final, dim3((T + 63) / 64), dim3(64), 0, st, T, nbk, (const double*)d_dxpart.get(),
+                               d_dxps.get() + (size_t)it * T);
+            hipLaunchKernelGGL(k_batch_metrics, dim3(MGADMM_NMETRIC), dim3(256), 0, st, (const double*)d_ps.get(), q.Bp, B,
+                               d_hist.get() + (size_t)it * MGADMM_NMETRIC,
+                               (hist && hist->metrics_per_sample) ? d_hist_ps.get() + (size_t)it * MGADMM_NMETRIC * B : nullptr);
             MG_HIP(hipGetLastError());
             b.swap_inner(has_zd);
             if (has_phi) std::swap(b.phc, b.phn);
@@ -1245,32 +1197,15 @@ struct Engine : EngineBase {
         const bool has_phi = this->has_phi(), has_zd = this->has_zd();
         const int n_outer = p.max_admm_iter, n_inner = p.max_inner_iter;
         const size_t rows_needed = (size_t)n_outer * n_inner;
-        if (rows_needed > (size_t)max_admm_alloc) {          // d_cg_iters holds one row of 3 x Bp counts per inner iteration
-            // the three history buffers grow together (max_admm_alloc is their common row count); the new ones are all
-            // allocated before an old one is released, so a failed allocation leaves the solver as it was
-            int* nc = nullptr;
-            double *nh = nullptr, *nd = nullptr;
-            const hipError_t e1 = hipMalloc(&nc, sizeof(int) * rows_needed * 3 * Bp_max);
-            const hipError_t e2 = e1 == hipSuccess ? hipMalloc(&nh, sizeof(double) * rows_needed * MGADMM_NMETRIC) : e1;
-            const hipError_t e3 = e2 == hipSuccess ? hipMalloc(&nd, sizeof(double) * rows_needed * T) : e2;
-            if (e3 != hipSuccess) {
-                if (nc) (void)hipFree(nc);
-                if (nh) (void)hipFree(nh);
-                if (nd) (void)hipFree(nd);
-                (void)hipGetLastError();
-                mg_set_error("two_loops: cannot allocate the CG-count history of %zu inner iterations x %d samples (%s)", rows_needed,
-                             Bp_max, hipGetErrorString(e3));
-                return MGADMM_ERR_NOMEM;
-            }
-            if (d_cg_iters) (void)hipFree(d_cg_iters);
-            if (d_hist) (void)hipFree(d_hist);
-            if (d_dxps) (void)hipFree(d_dxps);
-            d_cg_iters = nc; d_hist = nh; d_dxps = nd;
-            max_admm_alloc = (int)rows_needed;
+        if (const int e = alloc_iter_dependent(rows_needed)) {          // d_cg_iters holds one row of 3 x Bp counts per inner iteration
+            (void)hipGetLastError();
+            mg_set_error("two_loops: cannot allocate the CG-count history of %zu inner iterations x %d samples (%s)", rows_needed,
+                         Bp_max, mg_buf_error(e));
+            return MGADMM_ERR_NOMEM;
         }
-        MG_HIP(hipMemsetAsync(d_nonfinite, 0, sizeof(int), st));
-        MG_HIP(hipMemsetAsync(d_ps, 0, sizeof(double) * MGADMM_NMETRIC * q.Bp, st));
-        MG_HIP(hipMemsetAsync(d_cg_iters, 0, sizeof(int) * rows_needed * 3 * q.Bp, st));
+        MG_HIP(hipMemsetAsync(d_nonfinite.get(), 0, sizeof(int), st));
+        MG_HIP(hipMemsetAsync(d_ps.get(), 0, sizeof(double) * MGADMM_NMETRIC * q.Bp, st));
+        MG_HIP(hipMemsetAsync(d_cg_iters.get(), 0, sizeof(int) * rows_needed * 3 * q.Bp, st));
         Bufs b;
         const S* m = nullptr;
         MG_TRY(load_input(q, y, mask, mask_f32, true, vec[b.xc], &m));
@@ -1287,7 +1222,7 @@ struct Engine : EngineBase {
             MG_HIP(hipMemcpyAsync(vec[b.zdc], vec[b.xc], ne * sizeof(S), hipMemcpyDeviceToDevice, st));
             for (int in = 0; in < n_inner; ++in) {
                 // (no CG coefficients are recorded and EpiDual's fused norms are not kept: ADMM.py:488-490)
-                MG_TRY(admm_step(q, w, b, d_cg_iters + ((size_t)o * n_inner + in) * 3 * q.Bp, m, false, nullptr, 0));
+                MG_TRY(admm_step(q, w, b, d_cg_iters.get() + ((size_t)o * n_inner + in) * 3 * q.Bp, m, false, nullptr, 0));
                 b.swap_inner(has_zd);
             }
             if (has_phi) {          // phi = phi_direct(x, gamma); gamma += rho (phi - Ldr x)   (ADMM.py:497-504)
@@ -1302,9 +1237,9 @@ struct Engine : EngineBase {
             hist->n_iters = n_done;
             if (hist->cg_iters) MG_TRY(fetch_cg_iters(hist->cg_iters, rows_needed, B, q.Bp));
         }
-        MG_HIP(hipMemcpyAsync(h_flag, d_nonfinite, sizeof(int), hipMemcpyDeviceToHost, st));
+        MG_HIP(hipMemcpyAsync(h_flag.get(), d_nonfinite.get(), sizeof(int), hipMemcpyDeviceToHost, st));
         MG_HIP(hipStreamSynchronize(st));
-        if (h_flag[0]) {
+        if (h_flag.get()[0]) {
             mg_set_error("two_loops: NaN/Inf met in the iterates (cf. the asserts of ADMM.py:432-504)");
             return MGADMM_ERR_NONFINITE;
         }
@@ -1314,7 +1249,7 @@ struct Engine : EngineBase {
     // the CG counts of `rows` iterations: [rows][3][Bp] on the device -> out[rows][3][B]
     int fetch_cg_iters(int32_t* out, size_t rows, int B, int Bp) {
         std::vector<int> tmp(rows * 3 * Bp);
-        MG_HIP(hipMemcpyAsync(tmp.data(), d_cg_iters, sizeof(int) * tmp.size(), hipMemcpyDeviceToHost, st));
+        MG_HIP(hipMemcpyAsync(tmp.data(), d_cg_iters.get(), sizeof(int) * tmp.size(), hipMemcpyDeviceToHost, st));
         MG_HIP(hipStreamSynchronize(st));
         for (size_t r = 0; r < rows * 3; ++r) memcpy(out + r * B, tmp.data() + r * Bp, sizeof(int) * B);
         return MGADMM_OK;
@@ -1327,17 +1262,17 @@ struct Engine : EngineBase {
             if (hist->n_iters_per_sample)
                 for (int b = 0; b < B; ++b) hist->n_iters_per_sample[b] = nps ? nps[b] : n_done;
             if (hist->metrics)
-                MG_HIP(hipMemcpyAsync(hist->metrics, d_hist, sizeof(double) * (size_t)n_done * MGADMM_NMETRIC, hipMemcpyDeviceToHost, st));
+                MG_HIP(hipMemcpyAsync(hist->metrics, d_hist.get(), sizeof(double) * (size_t)n_done * MGADMM_NMETRIC, hipMemcpyDeviceToHost, st));
             if (hist->delta_x_per_step && !nps)
-                MG_HIP(hipMemcpyAsync(hist->delta_x_per_step, d_dxps, sizeof(double) * (size_t)n_done * T, hipMemcpyDeviceToHost, st));
+                MG_HIP(hipMemcpyAsync(hist->delta_x_per_step, d_dxps.get(), sizeof(double) * (size_t)n_done * T, hipMemcpyDeviceToHost, st));
             if (hist->metrics_per_sample)
-                MG_HIP(hipMemcpyAsync(hist->metrics_per_sample, d_hist_ps, sizeof(double) * (size_t)n_done * MGADMM_NMETRIC * B,
+                MG_HIP(hipMemcpyAsync(hist->metrics_per_sample, d_hist_ps.get(), sizeof(double) * (size_t)n_done * MGADMM_NMETRIC * B,
                                       hipMemcpyDeviceToHost, st));
             if (hist->cg_iters) MG_TRY(fetch_cg_iters(hist->cg_iters, n_done, B, Bp));
         }
-        MG_HIP(hipMemcpyAsync(h_flag, d_nonfinite, sizeof(int), hipMemcpyDeviceToHost, st));
+        MG_HIP(hipMemcpyAsync(h_flag.get(), d_nonfinite.get(), sizeof(int), hipMemcpyDeviceToHost, st));
         MG_HIP(hipStreamSynchronize(st));
-        if (rc_final == MGADMM_OK && h_flag[0]) rc_final = MGADMM_ERR_NONFINITE;
+        if (rc_final == MGADMM_OK && h_flag.get()[0]) rc_final = MGADMM_ERR_NONFINITE;
         if (rc_final == MGADMM_OK && hist && hist->metrics) {
             for (size_t k = 0; k < (size_t)n_done * MGADMM_NMETRIC; ++k)
                 if (!std::isfinite(hist->metrics[k])) rc_final = MGADMM_ERR_NONFINITE;
@@ -1351,8 +1286,8 @@ struct Engine : EngineBase {
         const size_t K = p.max_cg_iter;
         double* a = hist->cg_alpha + ((size_t)it * 3 + which) * K * B;
         double* b = hist->cg_beta + ((size_t)it * 3 + which) * K * B;
-        MG_TRY(fetch_hist(d_alpha_hist + (size_t)from * K * Bp, K * Bp, a, B, Bp, K));
-        return fetch_hist(d_beta_hist + (size_t)from * K * Bp, K * Bp, b, B, Bp, K);
+        MG_TRY(fetch_hist(d_alpha_hist.get() + (size_t)from * K * Bp, K * Bp, a, B, Bp, K));
+        return fetch_hist(d_beta_hist.get() + (size_t)from * K * Bp, K * Bp, b, B, Bp, K);
     }
 };
 

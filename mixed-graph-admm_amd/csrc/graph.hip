@@ -213,31 +213,21 @@ static int upload_csr(const HostCsr& h, DevCsr& d) {
     d.max_row = 0;
     for (int i = 0; i < h.n; ++i) d.max_row = std::max(d.max_row, h.rowptr[i + 1] - h.rowptr[i]);
     d.avg_row_ceil = h.n ? (d.nnz + h.n - 1) / h.n : 0;
-    MG_HIP(hipMalloc(&d.rowptr, sizeof(int) * (h.n + 1)));
     // CSR_PAD (8) zeroed extra entries: the row kernels read a fixed window of entries per row
-    MG_HIP(hipMalloc(&d.col, sizeof(int) * (d.nnz + 8)));
-    MG_HIP(hipMalloc(&d.val, sizeof(float) * (d.nnz + 8)));
-    MG_HIP(hipMemset(d.col, 0, sizeof(int) * (d.nnz + 8)));
-    MG_HIP(hipMemset(d.val, 0, sizeof(float) * (d.nnz + 8)));
-    MG_HIP(hipMemcpy(d.rowptr, h.rowptr.data(), sizeof(int) * (h.n + 1), hipMemcpyHostToDevice));
-    if (d.nnz) {
-        MG_HIP(hipMemcpy(d.col, h.col.data(), sizeof(int) * d.nnz, hipMemcpyHostToDevice));
-        MG_HIP(hipMemcpy(d.val, h.val.data(), sizeof(float) * d.nnz, hipMemcpyHostToDevice));
-    }
+    std::vector<int> col(h.col);
+    std::vector<float> val(h.val);
+    col.resize((size_t)d.nnz + 8, 0);
+    val.resize((size_t)d.nnz + 8, 0.f);
+    MG_BUF(d.rowptr.upload(h.rowptr));
+    MG_BUF(d.col.upload(col));
+    MG_BUF(d.val.upload(val));
     return MGADMM_OK;
-}
-
-static void free_csr(DevCsr& d) {
-    if (d.rowptr) (void)hipFree(d.rowptr);
-    if (d.col) (void)hipFree(d.col);
-    if (d.val) (void)hipFree(d.val);
-    d = DevCsr();
 }
 
 OpDesc mgadmm_graph::op_lu() const {
     OpDesc o{};
     o.kind = OPK_SPATIAL;
-    o.rowptr = Wu.rowptr; o.col = Wu.col; o.val = Wu.val;
+    o.rowptr = Wu.rowptr.get(); o.col = Wu.col.get(); o.val = Wu.val.get();
     o.shift = 0;
     o.self_mode = SELF_ONE;
     return o;
@@ -248,11 +238,11 @@ OpDesc mgadmm_graph::op_ldr() const {
     o.self_mode = SELF_LDR;
     if (mode == MGADMM_TEMPORAL_SPATIAL) {
         o.kind = OPK_SPATIAL;
-        o.rowptr = Wd.rowptr; o.col = Wd.col; o.val = Wd.val;
+        o.rowptr = Wd.rowptr.get(); o.col = Wd.col.get(); o.val = Wd.val.get();
         o.shift = -1;
     } else {
         o.kind = OPK_BAND;
-        o.band_w = band_w; o.skip = skip; o.band_dir = -1;
+        o.band_w = band_w.get(); o.skip = skip; o.band_dir = -1;
     }
     return o;
 }
@@ -262,12 +252,12 @@ OpDesc mgadmm_graph::op_ldrt() const {
     o.self_mode = SELF_LDRT;
     if (mode == MGADMM_TEMPORAL_SPATIAL) {
         o.kind = OPK_SPATIAL;
-        o.rowptr = WdT.rowptr; o.col = WdT.col; o.val = WdT.val;
+        o.rowptr = WdT.rowptr.get(); o.col = WdT.col.get(); o.val = WdT.val.get();
         o.shift = +1;
         o.q1 = q1;
     } else {
         o.kind = OPK_BAND;
-        o.band_w = band_w; o.skip = skip; o.band_dir = +1;
+        o.band_w = band_w.get(); o.skip = skip; o.band_dir = +1;
         o.q1 = 0;  // line-graph branches are exact transposes (ADMM.py:181-194)
     }
     return o;
@@ -325,15 +315,13 @@ extern "C" int mgadmm_graph_create(const mgadmm_graph_desc* d, mgadmm_graph** ou
         if (rc == MGADMM_OK) rc = up(g->hWdT, g->WdT);
     }
     if (rc == MGADMM_OK && g->mode == MGADMM_TEMPORAL_BAND) {
-        if (hipMalloc(&g->band_w, sizeof(float) * g->T * g->skip) != hipSuccess ||
-            hipMemcpy(g->band_w, d->band_w, sizeof(float) * g->T * g->skip, hipMemcpyHostToDevice) != hipSuccess) {
+        if (g->band_w.upload(std::vector<float>(d->band_w, d->band_w + (size_t)g->T * g->skip)) != 0) {
             mg_set_error("graph_create: band_w upload failed");
             rc = MGADMM_ERR_HIP;
         }
     }
     if (rc == MGADMM_OK && g->has_perm) {
-        if (hipMalloc(&g->d_perm, sizeof(int) * g->N) != hipSuccess ||
-            hipMemcpy(g->d_perm, g->perm.data(), sizeof(int) * g->N, hipMemcpyHostToDevice) != hipSuccess) {
+        if (g->d_perm.upload(g->perm) != 0) {
             mg_set_error("graph_create: perm upload failed");
             rc = MGADMM_ERR_HIP;
         }
@@ -347,11 +335,7 @@ extern "C" int mgadmm_graph_create(const mgadmm_graph_desc* d, mgadmm_graph** ou
 extern "C" int mgadmm_graph_destroy(mgadmm_graph* g) {
     if (!g) return MGADMM_OK;
     (void)hipSetDevice(g->device);
-    free_csr(g->Wu); free_csr(g->Wd); free_csr(g->WdT);
-    if (g->band_w) (void)hipFree(g->band_w);
-    if (g->d_perm) (void)hipFree(g->d_perm);
-    if (g->ln_rowsum) (void)hipFree(g->ln_rowsum);
-    delete g;
+    delete g;      // (the device tables go with their owners: DevCsr, band_w, d_perm, ln_rowsum)
     return MGADMM_OK;
 }
 

@@ -16,63 +16,51 @@ namespace {
 
 struct LdsEngine final : Engine<float> {
     int dev_cus = 0;               // compute units of the device (staggered start of k_admm_lds)
-    int* d_lds_csr = nullptr;
-    double* d_slice_sums = nullptr;   // [ceil(Bmax/64)][T*N]: delta_x_per_step, the sums of x - x_old over every 64-sample slice
+    DevBuf<int> d_lds_csr;
+    DevBuf<double> d_slice_sums;      // [ceil(Bmax/64)][T*N]: delta_x_per_step, the sums of x - x_old over every 64-sample slice
     // the whole-batch metric kernels (lds_args.h, mg_lds_metrics) beside a k_admm_lds launch and on an idle GPU
     LdsMetricShape metric_busy{64, 0}, metric_idle{256, 0};
     // ADMM outer loop of the LDS path without host round trips (solve_lds): device stop word, second metric buffer, helper
     // stream for the whole-batch metric kernels and the events that order the two streams
     int lds_async = 1;            // MGADMM_LDS_ASYNC=0: one stream, the host tests the stop criterion after every iteration
-    int* d_stop = nullptr;
-    double* d_ps_ring = nullptr;  // [LDS_SETS][J][NMETRIC][Bp]: per-sample metric sums of the chunked schedule
+    DevBuf<int> d_stop;
+    DevBuf<double> d_ps_ring;     // [LDS_SETS][J][NMETRIC][Bp]: per-sample metric sums of the chunked schedule
     // per-sample stop of the outer loop (MGADMM_ADMM_PER_SAMPLE)
-    int* d_pstop = nullptr;       // [Bp_max] stop words, [1] number of stopped samples, [Bp_max] iterations of every sample
-    double* d_ps_full = nullptr;  // [max_admm_iter][NMETRIC][Bp]: per-sample metric sums of every iteration (allocated on first use)
-    size_t ps_full_elems = 0;
+    DevBuf<int> d_pstop;          // [Bp_max] stop words, [1] number of stopped samples, [Bp_max] iterations of every sample
+    DevBuf<double> d_ps_full;     // [max_admm_iter][NMETRIC][Bp]: per-sample metric sums of every iteration (allocated on first use)
     // per-sample ADMM weights (mgadmm_solver_set_sample_params) and per-iteration weights (mgadmm_solver_set_param_schedule):
     // the device tables of the records k_admm_lds_pp reads (the caller's arrays: Engine::wt).  d_sp: wt.sp_B records, rebuilt
     // whenever the arrays or the scalars change; d_sch: wt.sch_rows x B records, formed when a solve starts and kept until
     // something it was formed from changes
-    LdsSampleParams* d_sp = nullptr;   // [Bmax]
-    LdsSampleParams* d_sch = nullptr;
-    size_t sch_elems = 0;
+    DevBuf<LdsSampleParams> d_sp;      // [Bmax]
+    DevBuf<LdsSampleParams> d_sch;
     int sch_up_B = 0;             // batch the device table was formed for; 0 = it has to be formed
     // adaptive penalties (Engine::ad, lds_adapt.h): per solve the table of max_admm_iter x B records k_lds_adapt writes between
     // the launches, the six weights of every sample as doubles and the history of the three penalties by period
-    LdsSampleParams* d_ad_tab = nullptr;
-    double *d_ad_w = nullptr, *d_ad_hist = nullptr;
-    size_t ad_tab_elems = 0, ad_w_elems = 0, ad_hist_elems = 0;
+    DevBuf<LdsSampleParams> d_ad_tab;
+    DevBuf<double> d_ad_w, d_ad_hist;
     int ad_last_B = 0;            // of the last solve that adapted (mgadmm_solver_get_adaptive_history)
     // per-sample graph weights (mgadmm_solver_set_sample_graphs, lds_graph_sets.h): the images of the sets back to back and the
     // set of every sample; the solver's own image and the planner's switches are kept for the comparison with every set
-    int* d_sg_img = nullptr;      // [sets][img_stride]
-    int* d_sg_set = nullptr;      // [Bp_max]
+    DevBuf<int> d_sg_img;         // [sets][img_stride]
+    DevBuf<int> d_sg_set;         // [Bp_max]
     std::vector<int> lds_img_host;
     // per-sample temporal band weights (mgadmm_solver_set_sample_bands, band_sets.h; the caller's arrays: Engine::bs): the
     // tables of the sets back to back and the set of every sample
-    float* d_bs_w = nullptr;      // [sets][T*skip]
-    int* d_bs_set = nullptr;      // [Bp_max]
+    DevBuf<float> d_bs_w;         // [sets][T*skip]
+    DevBuf<int> d_bs_set;         // [Bp_max]
     ldsplan::Switches lds_sw;
     // iterate buffers of solve_lds by slot number (lds_schedule.h): the 15 workspace vectors this path does not use otherwise
     // hold the LDS_SETS (J - 1) + LDS_NBOUND = 13 slots of J = 4; chunks longer than 4 iterations (up to LDS_MAXJ) get the
     // rest in lds_ring_extra on the first solve that asks for them, kept for the solver's lifetime
     static constexpr int ring_ids[] = {V_XA, V_XB, V_ZUB, V_ZDB, V_PHIB, V_Y, V_MASK, V_R, V_P, V_Q, V_AP, V_RHS, V_TMP, V_IO0, V_IO1};
     static constexpr int NRING = (int)(sizeof(ring_ids) / sizeof(ring_ids[0]));
-    std::vector<float*> lds_ring_extra;
-    hipStream_t st_side = nullptr;
-    hipEvent_t ev_main[LDS_NBOUND] = {nullptr}, ev_side[LDS_NBOUND] = {nullptr};
+    std::vector<DevBuf<float>> lds_ring_extra;
+    Stream st_side;
+    Event ev_main[LDS_NBOUND], ev_side[LDS_NBOUND];
 
     using Engine<float>::Engine;
-    ~LdsEngine() override {
-        (void)hipSetDevice(g->device);
-        auto fr = [](void* q) { if (q) (void)hipFree(q); };
-        fr(d_lds_csr); fr(d_slice_sums); fr(d_stop); fr(d_ps_ring); fr(d_pstop); fr(d_ps_full);
-        fr(d_sp); fr(d_sg_img); fr(d_sg_set); fr(d_bs_w); fr(d_bs_set); fr(d_sch); fr(d_ad_tab); fr(d_ad_w); fr(d_ad_hist);
-        for (float* b : lds_ring_extra) if (b) (void)hipFree(b);
-        if (st_side) (void)hipStreamDestroy(st_side);
-        for (auto& e : ev_main) if (e) (void)hipEventDestroy(e);
-        for (auto& e : ev_side) if (e) (void)hipEventDestroy(e);
-    }
+    ~LdsEngine() override { (void)hipSetDevice(g->device); }      // (before the members release, as in ~Engine)
 
     int init() override {
         MG_TRY(init_workspace());
@@ -104,8 +92,8 @@ struct LdsEngine final : Engine<float> {
     int upload_sample_params(int n) {
         std::vector<LdsSampleParams> rec;
         ldsparam::fill_records(wt.source(false, p), p.ablation, n, rec);      // (lds_param_table.h: one row, no schedule)
-        if (!d_sp) MG_HIP(hipMalloc(&d_sp, sizeof(LdsSampleParams) * (size_t)Bmax));
-        MG_HIP(hipMemcpy(d_sp, rec.data(), sizeof(LdsSampleParams) * rec.size(), hipMemcpyHostToDevice));
+        MG_BUF(d_sp.reserve((size_t)Bmax));
+        MG_BUF(d_sp.upload(rec));
         return MGADMM_OK;
     }
 
@@ -114,9 +102,7 @@ struct LdsEngine final : Engine<float> {
         MG_HIP(hipSetDevice(g->device));
         if ((sch == nullptr || n_rows == 0) && d_sch) {      // clears
             MG_HIP(hipDeviceSynchronize());
-            (void)hipFree(d_sch);
-            d_sch = nullptr;
-            sch_elems = 0;
+            d_sch.reset();
         }
         MG_TRY(Engine<float>::set_param_schedule(sch, n_rows, B, first_row));
         sch_up_B = 0;
@@ -127,8 +113,7 @@ struct LdsEngine final : Engine<float> {
         if (sch_up_B == B && d_sch) return MGADMM_OK;
         std::vector<LdsSampleParams> rec;
         ldsparam::fill_records(wt.source(true, p), p.ablation, B, rec);
-        MG_TRY(grow(d_sch, sch_elems, rec.size()));
-        MG_HIP(hipMemcpy(d_sch, rec.data(), sizeof(LdsSampleParams) * rec.size(), hipMemcpyHostToDevice));
+        MG_BUF(d_sch.upload(rec));
         sch_up_B = B;
         return MGADMM_OK;
     }
@@ -139,7 +124,7 @@ struct LdsEngine final : Engine<float> {
         if (ad_last_periods == 0 || rho_hist == nullptr || max_periods <= 0) return MGADMM_OK;
         MG_REQUIRE(B == ad_last_B, "get_adaptive_history: the last adaptive_rho solve had B = %d, not %d", ad_last_B, B);
         MG_HIP(hipSetDevice(g->device));
-        MG_HIP(hipMemcpy(rho_hist, d_ad_hist, sizeof(double) * 3 * (size_t)B * std::min(max_periods, ad_last_periods), hipMemcpyDeviceToHost));
+        MG_HIP(hipMemcpy(rho_hist, d_ad_hist.get(), sizeof(double) * 3 * (size_t)B * std::min(max_periods, ad_last_periods), hipMemcpyDeviceToHost));
         return MGADMM_OK;
     }
 
@@ -148,8 +133,7 @@ struct LdsEngine final : Engine<float> {
         MG_HIP(hipSetDevice(g->device));
         if (n_sets == 0 && d_sg_img) {
             MG_HIP(hipDeviceSynchronize());
-            (void)hipFree(d_sg_img);
-            d_sg_img = nullptr;
+            d_sg_img.reset();
         }
         MG_TRY(Engine<float>::set_sample_graphs(n_sets, graphs, set_of_sample, B));      // (n_sets == 0 clears; the checks, the gate)
         if (n_sets == 0) return MGADMM_OK;
@@ -167,18 +151,16 @@ struct LdsEngine final : Engine<float> {
         }
         std::vector<int> set_of((size_t)Bp_max, 0);
         std::copy(set_of_sample, set_of_sample + B, set_of.begin());
-        int* fresh = nullptr;
-        MG_HIP(hipMalloc(&fresh, sizeof(int) * table.size()));
-        if (hipMemcpy(fresh, table.data(), sizeof(int) * table.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(fresh);
+        DevBuf<int> fresh;      // (a local owner: whatever fails below, the new images are released)
+        MG_BUF(fresh.reserve(table.size()));
+        if (fresh.upload(table) != 0) {
             mg_set_error("set_sample_graphs: upload of the images failed");
             return MGADMM_ERR_HIP;
         }
-        if (!d_sg_set) MG_HIP(hipMalloc(&d_sg_set, sizeof(int) * (size_t)Bp_max));
+        MG_BUF(d_sg_set.reserve((size_t)Bp_max));
         MG_HIP(hipDeviceSynchronize());          // no launch reads the old table any more
-        MG_HIP(hipMemcpy(d_sg_set, set_of.data(), sizeof(int) * set_of.size(), hipMemcpyHostToDevice));
-        if (d_sg_img) (void)hipFree(d_sg_img);
-        d_sg_img = fresh;
+        MG_BUF(d_sg_set.upload(set_of));
+        d_sg_img = std::move(fresh);
         sg_B = B;
         return MGADMM_OK;
     }
@@ -186,14 +168,12 @@ struct LdsEngine final : Engine<float> {
     // The tables lie back to back as the caller gave them: workgroup b of k_admm_lds_pp reads the one of set d_bs_set[b]
     int set_sample_bands(int n_sets, const float* band_w, const int32_t* set_of_sample, int B) override {
         MG_TRY(Engine<float>::set_sample_bands(n_sets, band_w, set_of_sample, B));      // (the checks; synchronises; clears)
-        if (d_bs_w) (void)hipFree(d_bs_w);
-        d_bs_w = nullptr;
+        d_bs_w.reset();
         if (bs.B == 0) return MGADMM_OK;
         const std::vector<int32_t> set_of = bs.padded_set_of(Bp_max);
-        if (!d_bs_set) MG_HIP(hipMalloc(&d_bs_set, sizeof(int) * (size_t)Bp_max));
-        MG_HIP(hipMalloc(&d_bs_w, sizeof(float) * bs.w.size()));
-        MG_HIP(hipMemcpy(d_bs_w, bs.w.data(), sizeof(float) * bs.w.size(), hipMemcpyHostToDevice));
-        MG_HIP(hipMemcpy(d_bs_set, set_of.data(), sizeof(int) * set_of.size(), hipMemcpyHostToDevice));
+        MG_BUF(d_bs_set.reserve((size_t)Bp_max));
+        MG_BUF(d_bs_w.upload(bs.w));
+        MG_BUF(d_bs_set.upload(set_of));
         return MGADMM_OK;
     }
 
@@ -210,19 +190,17 @@ struct LdsEngine final : Engine<float> {
             return MGADMM_ERR_INVALID;
         }
         if (planned == ldsplan::NO_PLAN) return MGADMM_OK;
-        MG_HIP(hipMalloc(&d_lds_csr, sizeof(int) * img.size()));
-        MG_HIP(hipMemcpy(d_lds_csr, img.data(), sizeof(int) * img.size(), hipMemcpyHostToDevice));
+        MG_BUF(d_lds_csr.upload(img));
         lds_img_host = img;
-        MG_HIP(hipMalloc(&d_slice_sums, sizeof(double) * T * N * ((size_t)(Bmax + 63) / 64)));
+        MG_BUF(d_slice_sums.reserve((size_t)T * N * ((size_t)(Bmax + 63) / 64)));
         // MGADMM_LDS_METRIC_SHAPE=<threads>x<workgroups> (workgroups 0: one task per thread): the busy shape, for experiments
         if (const char* e = getenv("MGADMM_LDS_METRIC_SHAPE")) {
             int nt = 0, wgs = 0;
             if (sscanf(e, "%dx%d", &nt, &wgs) == 2 && (nt == 64 || nt == 256 || nt == 512) && wgs >= 0) metric_busy = LdsMetricShape{nt, wgs};
         }
-        MG_HIP(hipMalloc(&d_stop, sizeof(int)));
-        MG_HIP(hipMemset(d_stop, 0, sizeof(int)));
-        MG_HIP(hipMalloc(&d_ps_ring, sizeof(double) * LDS_SETS * LDS_MAXJ * MGADMM_NMETRIC * Bp_max));
-        MG_HIP(hipMalloc(&d_pstop, sizeof(int) * (2 * (size_t)Bp_max + 1)));
+        MG_BUF(d_stop.upload({0}));
+        MG_BUF(d_ps_ring.reserve((size_t)LDS_SETS * LDS_MAXJ * MGADMM_NMETRIC * Bp_max));
+        MG_BUF(d_pstop.reserve(2 * (size_t)Bp_max + 1));
         {
             // helper stream of the overlapped outer loop: non-blocking (the caller's stream may be the legacy default stream,
             // which would serialise a blocking stream with itself), lowest priority (the k_admm_lds workgroups of the next
@@ -230,15 +208,15 @@ struct LdsEngine final : Engine<float> {
             int lo = 0, hi = 0;
             MG_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
             if (const char* e = getenv("MGADMM_LDS_SIDE_PRIO")) lo = atoi(e) > 0 ? hi : lo;
-            MG_HIP(hipStreamCreateWithPriority(&st_side, hipStreamNonBlocking, lo));
-            for (auto& e : ev_main) MG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            for (auto& e : ev_side) MG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            MG_HIP(hipStreamCreateWithPriority(st_side.put(), hipStreamNonBlocking, lo));
+            for (auto& e : ev_main) MG_HIP(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
+            for (auto& e : ev_side) MG_HIP(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
         }
         return MGADMM_OK;
     }
 
     // row_of_node on the device for the kernels that convert between node order and the thread-major state (nullptr: identity)
-    const int* lds_row_of_node() const { return lds.row_order ? d_lds_csr + lds.off_rown : nullptr; }
+    const int* lds_row_of_node() const { return lds.row_order ? d_lds_csr.get() + lds.off_rown : nullptr; }
 
     int launch_lds(const LdsArgs& a, int B) {
         const bool timed = prof_open(0, 0.0);
@@ -263,14 +241,14 @@ struct LdsEngine final : Engine<float> {
     // buffer of an iterate slot; slots beyond the workspace vectors are allocated here
     int lds_ring_reserve(int slots) {
         while (NRING + (int)lds_ring_extra.size() < slots) {
-            float* b = nullptr;
-            MG_HIP(hipMalloc(&b, vec_elems * sizeof(float)));
-            lds_ring_extra.push_back(b);
+            DevBuf<float> b;
+            MG_BUF(b.reserve(vec_elems));
+            lds_ring_extra.push_back(std::move(b));
             ws_bytes += (int64_t)(vec_elems * sizeof(float));
         }
         return MGADMM_OK;
     }
-    float* lds_ring(int slot) const { return slot < NRING ? vec[ring_ids[slot]] : lds_ring_extra[slot - NRING]; }
+    float* lds_ring(int slot) const { return slot < NRING ? vec[ring_ids[slot]] : lds_ring_extra[slot - NRING].get(); }
     // iterate k (k = 0: the initial guess)
     float* lds_xbuf(const LdsRun& r, int k) const {
         const int slot = r.s.slot_of_iterate(k);
@@ -294,11 +272,11 @@ struct LdsEngine final : Engine<float> {
         a.rho = (float)p.rho; a.rho_u = (float)p.rho_u; a.rho_d = (float)p.rho_d;
         a.mu_u = (float)p.mu_u; a.mu_d1 = (float)p.mu_d1; a.mu_d2 = (float)p.mu_d2;
         a.cg_tol2 = p.cg_tol * p.cg_tol;
-        a.csr = d_lds_csr; a.lds_img0 = lds.lds_img0; a.lds_img_ints = lds.lds_img_ints;
+        a.csr = d_lds_csr.get(); a.lds_img0 = lds.lds_img0; a.lds_img_ints = lds.lds_img_ints;
         a.off_rp_u = lds.off_rp_u; a.off_rp_d = lds.off_rp_d;
         a.off_en_u = lds.off_en_u; a.off_en_d = lds.off_en_d; a.off_lead_t = lds.off_lead_t; a.off_tail_t = lds.off_tail_t; a.off_diag = lds.off_diag;
         a.npos = lds.npos_word; a.off_node = lds.off_node;
-        a.band_w = g->band_w;
+        a.band_w = g->band_w.get();
         a.zu = vec[V_ZUA]; a.zd = vec[V_ZDA]; a.phi = vec[V_PHIA];
         a.gam = vec[V_GAM]; a.gu = vec[V_GU]; a.gd = vec[V_GD];
         // staggered start (k_admm_lds): only when the launch runs several rounds of workgroups per CU
@@ -308,8 +286,8 @@ struct LdsEngine final : Engine<float> {
         a.stagger_wgs = ncu;
         a.stagger_ticks = (r.B >= 2 * ncu && us > 0) ? us * 100 : 0;
         a.y = (const float*)y; a.mask = (const float*)mask;
-        a.alpha_hist = r.record ? d_alpha_hist : nullptr; a.beta_hist = r.record ? d_beta_hist : nullptr;
-        a.nonfinite = d_nonfinite;
+        a.alpha_hist = r.record ? d_alpha_hist.get() : nullptr; a.beta_hist = r.record ? d_beta_hist.get() : nullptr;
+        a.nonfinite = d_nonfinite.get();
     }
 
     // iterate 0 and the state: a warm start is converted into the thread-major layout, a cold start forms ADMM.py:528-544
@@ -320,7 +298,7 @@ struct LdsEngine final : Engine<float> {
             float tm, den;
             time_moments(tm, den);
             return mg_lds_init(a.mask != nullptr, T, p.t_in, N, lds.TPG, r.B, tm, den, a.y, a.mask, x, a.zu, a.zd, a.gam, a.gu, a.gd,
-                               d_nonfinite, lds_row_of_node(), st);
+                               d_nonfinite.get(), lds_row_of_node(), st);
         }
         if (x0 != nullptr && x != x0) MG_HIP(hipMemcpyAsync(x, x0, (size_t)r.B * T * N * sizeof(float), hipMemcpyDeviceToDevice, st));
         auto in = [&](float* dst, const void* src) {
@@ -356,9 +334,9 @@ struct LdsEngine final : Engine<float> {
         LdsMetricArgs m;
         m.T = T; m.N = N; m.B = r.B; m.Bp = r.Bp;
         m.x = lds_xbuf(r, it + 1); m.xo = lds_xbuf(r, it);
-        m.scratch = d_slice_sums; m.dxps = d_dxps + (size_t)it * T; m.stop = r.a.stop;
-        m.ps = ps; m.out = d_hist + (size_t)it * MGADMM_NMETRIC;
-        m.out_ps = per_sample ? d_hist_ps + (size_t)it * MGADMM_NMETRIC * r.B : nullptr;
+        m.scratch = d_slice_sums.get(); m.dxps = d_dxps.get() + (size_t)it * T; m.stop = r.a.stop;
+        m.ps = ps; m.out = d_hist.get() + (size_t)it * MGADMM_NMETRIC;
+        m.out_ps = per_sample ? d_hist_ps.get() + (size_t)it * MGADMM_NMETRIC * r.B : nullptr;
         return mg_lds_metrics(m, busy ? metric_busy : metric_idle, s);
     }
 
@@ -366,12 +344,12 @@ struct LdsEngine final : Engine<float> {
     // to the pinned ring, and *word is what it was after step c - LAG (0 while there is no such step): ldssched::lag_step
     int lagged_word(int c, const int* d_word, int* word) {
         const ldssched::LagStep l = ldssched::lag_step(c, LAG);
-        MG_HIP(hipMemcpyAsync(h_flag + 1 + l.put, d_word, sizeof(int), hipMemcpyDeviceToHost, st));
+        MG_HIP(hipMemcpyAsync(h_flag.get() + 1 + l.put, d_word, sizeof(int), hipMemcpyDeviceToHost, st));
         MG_HIP(hipEventRecord(ev_ring[l.put], st));
         *word = 0;
         if (l.get >= 0) {
             MG_HIP(hipEventSynchronize(ev_ring[l.get]));
-            *word = h_flag[1 + l.get];
+            *word = h_flag.get()[1 + l.get];
         }
         return MGADMM_OK;
     }
@@ -389,13 +367,11 @@ struct LdsEngine final : Engine<float> {
         for (int f = 0; f < ldsparam::NW; ++f)
             for (int b = 0; b < B; ++b) w[(size_t)f * B + b] = ldsparam::weight_of(src, f, 0, b);
         const size_t hist_rows = (size_t)max_it / ad.every + 2;
-        MG_TRY(grow(d_ad_tab, ad_tab_elems, rec.size()));
-        MG_TRY(grow(d_ad_w, ad_w_elems, w.size()));
-        MG_TRY(grow(d_ad_hist, ad_hist_elems, hist_rows * 3 * B));
-        MG_HIP(hipMemcpy(d_ad_tab, rec.data(), sizeof(LdsSampleParams) * rec.size(), hipMemcpyHostToDevice));
-        MG_HIP(hipMemcpy(d_ad_w, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice));
-        MG_HIP(hipMemcpy(d_ad_hist, w.data(), sizeof(double) * 3 * B, hipMemcpyHostToDevice));
-        MG_HIP(hipMemsetAsync(d_ad_hist + (size_t)3 * B, 0xFF, sizeof(double) * (hist_rows - 1) * 3 * B, st));      // (all bits set: a NaN)
+        MG_BUF(d_ad_tab.upload(rec));
+        MG_BUF(d_ad_w.upload(w));
+        MG_BUF(d_ad_hist.reserve(hist_rows * 3 * B));
+        MG_HIP(hipMemcpy(d_ad_hist.get(), w.data(), sizeof(double) * 3 * B, hipMemcpyHostToDevice));
+        MG_HIP(hipMemsetAsync(d_ad_hist.get() + (size_t)3 * B, 0xFF, sizeof(double) * (hist_rows - 1) * 3 * B, st));      // (all bits set: a NaN)
         ad_last_B = B;
         return MGADMM_OK;
     }
@@ -406,8 +382,8 @@ struct LdsEngine final : Engine<float> {
         const ldsadapt::Rows rows = ldsadapt::rows_after(it, ad_start, ad.every, ad.until, r.s.max_it);
         r.ad_bounds.push_back(it + 1);
         LdsAdaptArgs k;
-        k.ps = ps; k.pstop = r.a.pstop; k.w = d_ad_w; k.table = d_ad_tab;
-        k.hist = d_ad_hist + r.ad_bounds.size() * 3 * (size_t)r.B;
+        k.ps = ps; k.pstop = r.a.pstop; k.w = d_ad_w.get(); k.table = d_ad_tab.get();
+        k.hist = d_ad_hist.get() + r.ad_bounds.size() * 3 * (size_t)r.B;
         k.B = r.B; k.Bp = r.Bp; k.row_first = rows.first; k.row_last = rows.last;
         k.ablation = p.ablation; k.has_phi = r.has_phi; k.has_zd = r.has_zd;
         k.q = ad;
@@ -425,10 +401,10 @@ struct LdsEngine final : Engine<float> {
             a.first = ch.it0 == 0 && r.cold;      // phi = Ldr x0 is formed by the first iteration of a cold start
             a.J = ch.Jc;
             for (int k = 0; k <= ch.Jc; ++k) a.xs[k] = lds_xbuf(r, ch.it0 + k);
-            a.cg_iters = d_cg_iters + (size_t)ch.it0 * 3 * r.Bp;
+            a.cg_iters = d_cg_iters.get() + (size_t)ch.it0 * 3 * r.Bp;
             a.it0 = ch.it0;                       // (read with the per-sample stop and with a schedule of weights)
             if (r.s.per_sample) {
-                a.ps = d_ps_full + (size_t)ch.it0 * row;
+                a.ps = d_ps_full.get() + (size_t)ch.it0 * row;
                 MG_TRY(launch_lds(a, r.B));
                 MG_TRY(adapt_step(r, ch.it0 + ch.Jc - 1, a.ps + (size_t)(ch.Jc - 1) * row));      // (the sums of every iteration are kept)
                 r.n_done = ch.it0 + ch.Jc;
@@ -437,7 +413,7 @@ struct LdsEngine final : Engine<float> {
                 if (stopped == r.B) break;        // the launches enqueued since returned at their guards
                 continue;
             }
-            a.ps = d_ps_ring + (size_t)ch.set * r.s.J * row;
+            a.ps = d_ps_ring.get() + (size_t)ch.set * r.s.J * row;
             if (ch.wait >= 0) MG_HIP(hipStreamWaitEvent(st, ev_side[ch.wait], 0));
             MG_TRY(launch_lds(a, r.B));
             MG_HIP(hipEventRecord(ev_main[ch.ev], st));
@@ -464,13 +440,13 @@ struct LdsEngine final : Engine<float> {
             a.first = it == 0 && r.cold;          // phi = Ldr x0 is formed by the first launch of a cold start
             a.J = 1;
             a.xs[0] = lds_xbuf(r, it); a.xs[1] = lds_xbuf(r, it + 1);
-            a.cg_iters = d_cg_iters + (size_t)it * 3 * r.Bp;
-            a.ps = d_ps;
+            a.cg_iters = d_cg_iters.get() + (size_t)it * 3 * r.Bp;
+            a.ps = d_ps.get();
             a.it0 = it;                           // (read with the per-sample stop and with a schedule of weights)
-            if (r.s.per_sample) a.ps = d_ps_full + (size_t)it * MGADMM_NMETRIC * r.Bp;
+            if (r.s.per_sample) a.ps = d_ps_full.get() + (size_t)it * MGADMM_NMETRIC * r.Bp;
             if (r.record) {
-                MG_TRY(fill(d_alpha_hist, 3 * K * r.Bp, (float)NAN));
-                MG_TRY(fill(d_beta_hist, 3 * K * r.Bp, (float)NAN));
+                MG_TRY(fill(d_alpha_hist.get(), 3 * K * r.Bp, (float)NAN));
+                MG_TRY(fill(d_beta_hist.get(), 3 * K * r.Bp, (float)NAN));
             }
             MG_TRY(launch_lds(a, r.B));
             MG_TRY(adapt_step(r, it, a.ps));
@@ -481,13 +457,13 @@ struct LdsEngine final : Engine<float> {
             }
             r.n_done = it + 1;
             if (r.s.per_sample) {         // (the host is in step with the device here: the count of this very launch)
-                MG_HIP(hipMemcpyAsync(h_flag + 1, a.pstop_count, sizeof(int), hipMemcpyDeviceToHost, st));
+                MG_HIP(hipMemcpyAsync(h_flag.get() + 1, a.pstop_count, sizeof(int), hipMemcpyDeviceToHost, st));
                 MG_HIP(hipStreamSynchronize(st));
-                if (h_flag[1] == r.B) break;
+                if (h_flag.get()[1] == r.B) break;
             } else if (r.s.kind == ldssched::DEVSTOP) {
                 int sw = 0;
-                MG_TRY(mg_lds_stop_test(d_hist + (size_t)it * MGADMM_NMETRIC, d_nonfinite, r.has_phi, r.has_zd, p.admm_tol, it, d_stop, st));
-                MG_TRY(lagged_word(it, d_stop, &sw));
+                MG_TRY(mg_lds_stop_test(d_hist.get() + (size_t)it * MGADMM_NMETRIC, d_nonfinite.get(), r.has_phi, r.has_zd, p.admm_tol, it, d_stop.get(), st));
+                MG_TRY(lagged_word(it, d_stop.get(), &sw));
                 if (sw != 0) break;       // the launches enqueued since returned at their guards
             } else if (p.check_stop) {
                 bool stop = false;
@@ -498,9 +474,9 @@ struct LdsEngine final : Engine<float> {
         if (r.s.kind == ldssched::DEVSTOP) {
             // the stop word after everything enqueued has run: 0 = no stop (all enqueued iterations ran), k > 0 = the stop
             // test passed at the end of iteration k - 1, k < 0 = iteration -k - 1 met a NaN / Inf
-            MG_HIP(hipMemcpyAsync(h_flag + 1, d_stop, sizeof(int), hipMemcpyDeviceToHost, st));
+            MG_HIP(hipMemcpyAsync(h_flag.get() + 1, d_stop.get(), sizeof(int), hipMemcpyDeviceToHost, st));
             MG_HIP(hipStreamSynchronize(st));
-            const int sw = h_flag[1];
+            const int sw = h_flag.get()[1];
             if (sw > 0) r.n_done = sw;
             else if (sw < 0) { r.n_done = -sw; r.rc = MGADMM_ERR_NONFINITE; }
         }
@@ -510,9 +486,9 @@ struct LdsEngine final : Engine<float> {
     // per-sample stop: r.n_done iterations were enqueued; the history from the stop words and the per-sample sums, the
     // iterations of every sample to `nps`, the largest of them to r.n_done
     int lds_finish_per_sample(LdsRun& r, std::vector<int>& nps) {
-        int* const d_nps = d_pstop + Bp_max + 1;
-        MG_TRY(mg_lds_ps_history(d_ps_full, d_pstop, r.n_done, r.s.max_it, r.B, r.Bp, d_nps, d_hist,
-                                 (r.hist && r.hist->metrics_per_sample) ? d_hist_ps : nullptr, st));
+        int* const d_nps = d_pstop.get() + Bp_max + 1;
+        MG_TRY(mg_lds_ps_history(d_ps_full.get(), d_pstop.get(), r.n_done, r.s.max_it, r.B, r.Bp, d_nps, d_hist.get(),
+                                 (r.hist && r.hist->metrics_per_sample) ? d_hist_ps.get() : nullptr, st));
         nps.resize(r.B);
         MG_HIP(hipMemcpyAsync(nps.data(), d_nps, sizeof(int) * r.B, hipMemcpyDeviceToHost, st));
         MG_HIP(hipStreamSynchronize(st));
@@ -539,39 +515,39 @@ struct LdsEngine final : Engine<float> {
         const ldssched::Schedule& s = r.s;
         const bool chunked = s.kind == ldssched::CHUNKS;
         MG_TRY(ensure_hist_ps(hist, B));
-        MG_HIP(hipMemsetAsync(d_nonfinite, 0, sizeof(int), st));
-        MG_HIP(hipMemsetAsync(d_ps, 0, sizeof(double) * MGADMM_NMETRIC * r.Bp, st));
-        MG_HIP(hipMemsetAsync(d_cg_iters, 0, sizeof(int) * (size_t)s.max_it * 3 * r.Bp, st));
+        MG_HIP(hipMemsetAsync(d_nonfinite.get(), 0, sizeof(int), st));
+        MG_HIP(hipMemsetAsync(d_ps.get(), 0, sizeof(double) * MGADMM_NMETRIC * r.Bp, st));
+        MG_HIP(hipMemsetAsync(d_cg_iters.get(), 0, sizeof(int) * (size_t)s.max_it * 3 * r.Bp, st));
         if (s.per_sample) {
-            MG_TRY(grow(d_ps_full, ps_full_elems, (size_t)s.max_it * MGADMM_NMETRIC * r.Bp));
-            MG_HIP(hipMemsetAsync(d_pstop, 0, sizeof(int) * ((size_t)Bp_max + 1), st));
+            MG_BUF(d_ps_full.reserve((size_t)s.max_it * MGADMM_NMETRIC * r.Bp));
+            MG_HIP(hipMemsetAsync(d_pstop.get(), 0, sizeof(int) * ((size_t)Bp_max + 1), st));
         }
         MG_TRY(lds_ring_reserve(s.slots()));
         lds_fill_args(r, y, mask);
         MG_TRY(lds_state_in(r, x0, state_in));
         if (s.kind == ldssched::DEVSTOP) {
-            r.a.stop = d_stop;
-            MG_HIP(hipMemsetAsync(d_stop, 0, sizeof(int), st));
+            r.a.stop = d_stop.get();
+            MG_HIP(hipMemsetAsync(d_stop.get(), 0, sizeof(int), st));
         }
-        if (chunked && !s.per_sample) MG_HIP(hipMemsetAsync(d_ps_ring, 0, sizeof(double) * LDS_SETS * s.J * MGADMM_NMETRIC * r.Bp, st));
+        if (chunked && !s.per_sample) MG_HIP(hipMemsetAsync(d_ps_ring.get(), 0, sizeof(double) * LDS_SETS * s.J * MGADMM_NMETRIC * r.Bp, st));
         if (s.per_sample) {
-            r.a.pstop = d_pstop; r.a.pstop_count = d_pstop + Bp_max; r.a.x_final = r.xo; r.a.admm_tol = p.admm_tol;
+            r.a.pstop = d_pstop.get(); r.a.pstop_count = d_pstop.get() + Bp_max; r.a.x_final = r.xo; r.a.admm_tol = p.admm_tol;
         }
         if (sg_B > 0) {                   // (B == sg_B: solve_gate) workgroup b reads the image of set d_sg_set[b]
-            r.a.csr = d_sg_img; r.a.img_stride = ldssets::img_stride(lds); r.a.gset = d_sg_set;
+            r.a.csr = d_sg_img.get(); r.a.img_stride = ldssets::img_stride(lds); r.a.gset = d_sg_set.get();
         }
         // the table of records the launches read (with one they take the kernels k_admm_lds_pp); trip k of a launch reads
         // row sched_row(it0 + k, sp_row0, sp_rows) of it
         if (bs.B > 0) {                   // (B == bs.B: bandsets::solve_gate) workgroup b reads the band table of set d_bs_set[b]
-            r.a.band_w = d_bs_w; r.a.bset = d_bs_set;
+            r.a.band_w = d_bs_w.get(); r.a.bset = d_bs_set.get();
         }
         const solvegate::TableChoice tc = bandsets::table_of(solvegate::table_of(set_state(), wt.sch_row0, s.max_it), bs);
         if (tc.scalar_records) MG_TRY(upload_sample_params(B));      // (a graph or band table without a weights table)
         switch (tc.table) {
             case solvegate::TABLE_NONE: break;
-            case solvegate::TABLE_SAMPLE: r.a.sp = d_sp; break;      // (B == sp_B: solve_gate)
-            case solvegate::TABLE_SCHEDULE: MG_TRY(upload_param_schedule(B)); r.a.sp = d_sch; break;
-            case solvegate::TABLE_ADAPTIVE: MG_TRY(adapt_begin(r)); r.a.sp = d_ad_tab; break;      // the steps between the launches write it
+            case solvegate::TABLE_SAMPLE: r.a.sp = d_sp.get(); break;      // (B == sp_B: solve_gate)
+            case solvegate::TABLE_SCHEDULE: MG_TRY(upload_param_schedule(B)); r.a.sp = d_sch.get(); break;
+            case solvegate::TABLE_ADAPTIVE: MG_TRY(adapt_begin(r)); r.a.sp = d_ad_tab.get(); break;      // the steps between the launches write it
         }
         r.a.sp_rows = tc.sp_rows; r.a.sp_row0 = tc.sp_row0; r.a.sp_stride = tc.stride_B ? B : 0;
         MG_TRY(chunked ? lds_run_chunks(r) : lds_run_steps(r));

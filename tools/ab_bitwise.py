@@ -4,6 +4,8 @@ under its own `timeout`, runs on the cfg2 tables
   - the streaming path (path='stream', B=64, 3 iterations), float32 and float64: ablation None and masked DGLR, one solve that
     records the CG coefficients, one with a shared param_schedule, one resumed from the state the plain solve returned, and
     two_loops with 2 outer x 2 inner iterations;
+  - cfg3 (N = 10000, B = 512, float32: the tiled and fused streaming kernels), 3 iterations;
+  - a float64 line-graph instance of width 3 on the cfg2 tables, 12 samples under the band tables of intervals 1, 2, 3;
 and the parent compares x, the exported state, the residual history, the CG counts and the recorded coefficients.
       python tools/ab_bitwise.py <lib A> <lib B>"""
 import os, subprocess, sys, tempfile
@@ -77,6 +79,18 @@ for dtype, tag in ((torch.float32, "f32"), (torch.float64, "f64")):
         blk.two_loops(y, mask=m)
         keep(name + "_two_loops", blk)
         blk.close()
+
+n3, B3, cl3, dl3, info3, _ = bench.build_problem("cfg3")
+blk = bench.make_solver(n3, cl3, dl3, info3, dev)
+blk.max_ADMM_iter = 3
+keep("cfg3", blk, blk.solve(bench.synth_y(n3, B3, 12, seed=1, offset=0, device=dev))[0])
+blk.close()
+
+blk = mgadmm.ADMM_algorithm({"n_nodes": n}, info, use_kNN=True, k=4, u_sigma=50, tables=(cl, dl), device=dev, compute_dtype=torch.float64,
+                            use_line_graph=True, skip_connection=3, path="stream")
+blk.check_stop, blk.max_ADMM_iter = False, 3
+keep("band_f64", blk, blk.solve(inputs(12, False, torch.float64)[0], band_params={"skip": [1, 2, 3] * 4})[0])
+blk.close()
 np.savez(OUT, **out)
 '''
 
