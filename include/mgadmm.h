@@ -159,7 +159,8 @@ typedef struct mgadmm_solver mgadmm_solver;
  * n_iters_per_sample): a caller built against an older header must be rebuilt -- compare the string before passing structs.
  * The patch number counts additions that leave every struct alone (0.3.1: mgadmm_solver_set_sample_params;
  * 0.3.2: mgadmm_solver_set_sample_graphs; 0.3.3: mgadmm_solver_set_param_schedule;
- * 0.3.4: mgadmm_solver_set_adaptive_rho, mgadmm_solver_get_adaptive_history; 0.3.5: mgadmm_solver_set_sample_bands). */
+ * 0.3.4: mgadmm_solver_set_adaptive_rho, mgadmm_solver_get_adaptive_history; 0.3.5: mgadmm_solver_set_sample_bands;
+ * 0.3.6: mgadmm_graph_set_time_weights). */
 const char* mgadmm_version(void);
 const char* mgadmm_last_error(void);
 
@@ -171,6 +172,21 @@ int mgadmm_graph_transpose_nnz(const mgadmm_graph* g, int32_t* nnz);
 int mgadmm_graph_get_transpose(const mgadmm_graph* g, int32_t* rowptr, int32_t* col, float* val);
 /* test hook: internal node order (perm[i] = API node stored at internal row i) */
 int mgadmm_graph_get_perm(const mgadmm_graph* g, int32_t* perm);
+
+/* Time-varying edge weights (kNN / physical graphs): slice s of W_u weighs the edges inside time step s (ADMM.py:147, u_ew of
+ * shape (T, N, k)), slice s of W_d the edges from time step s to s + 1 (ADMM.py:171, 200, 214, d_ew of shape (T-1, N, k+1)):
+ * Ldr at time t reads slice t - 1, Ldr^T at time t the transpose of slice t (W_d itself under transpose_by_gather).
+ * u_val_t: host floats [n_u_slices][nnz of W_u], d_val_t: [n_d_slices][nnz of W_d], each slice on the pattern (row pointers,
+ * column indices) given to mgadmm_graph_create; the arrays are copied.  Either may be NULL: that matrix keeps the one table of
+ * mgadmm_graph_create for every time step.  Call it before a solver is created on the graph (later -> MGADMM_ERR_INVALID).
+ *   - n_u_slices != T, n_d_slices != T - 1, or a value that is not finite -> MGADMM_ERR_INVALID (the message names the table and
+ *     [slice][entry]); a MGADMM_TEMPORAL_BAND graph -> MGADMM_ERR_UNSUPPORTED.
+ * A solver on such a graph runs the streaming path with the plain row kernels (the plan MGADMM_TILE=0 gives the graph; the
+ * operators with a table run k_rows_tv): mgadmm_apply, mgadmm_lhs, mgadmm_cg, mgadmm_phi_direct, mgadmm_solve and
+ * mgadmm_solve_from in both scalar types.  MGADMM_Q_LDS_OK is 0, so MGADMM_PATH_LDS and every feature of the LDS-resident path
+ * are refused as for any graph that path cannot hold.  mgadmm_apply(MGADMM_OP_LN), mgadmm_two_loops and
+ * mgadmm_solver_set_sample_graphs -> MGADMM_ERR_UNSUPPORTED (the messages contain "time-varying"). */
+int mgadmm_graph_set_time_weights(mgadmm_graph* g, const float* u_val_t, int32_t n_u_slices, const float* d_val_t, int32_t n_d_slices);
 
 /* allocates every workspace once for batches up to max_batch */
 int mgadmm_solver_create(mgadmm_graph* g, const mgadmm_params* p, int32_t max_batch, mgadmm_solver** out);

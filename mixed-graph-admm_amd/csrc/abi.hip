@@ -30,6 +30,7 @@ int mgadmm_solver_create(mgadmm_graph* g, const mgadmm_params* p, int32_t max_ba
         delete s;
         return rc;
     }
+    g->solvers++;      // (mgadmm_graph_set_time_weights: the tables are set before the first solver plans on the graph)
     *out = s;
     return MGADMM_OK;
 }

@@ -100,6 +100,10 @@ struct OpDesc {
     int q1;               // SELF_LDRT: keep the identity on the t=0 block (quirk Q1)
     const double* self_w; // optional per-row factor of the self coefficient (apply_op_Ln: row sums of d_ew); plain row kernel only
     const float* band_wb; // BAND, optional: [T*skip][Bp] a weight per batch column (mgadmm_solver_set_sample_bands) instead of band_w
+    // SPATIAL, optional: time-varying weights (mgadmm_graph_set_time_weights, tv_values.h).  No kernel but k_rows_tv reads them
+    const float* val_t;   // [n_slices][slice_stride] values per time slice on the pattern rowptr / col, then CSR_PAD entries
+    int slice_stride;     // entries of a slice (= nnz)
+    int n_slices;         // T (Lu) or T-1 (Ldr, Ldr^T)
 };
 
 struct mgadmm_graph {
@@ -114,6 +118,11 @@ struct mgadmm_graph {
     DevBuf<float> band_w;          // device
     DevBuf<double> ln_rowsum;      // device, internal order: sum_j d_ew[i,j] (self coefficient of apply_op_Ln), built on first use
     DevBuf<int> d_perm;            // device (empty when identity)
+    // time-varying weights (mgadmm_graph_set_time_weights): per-slice value tables in the internal node order on the patterns
+    // of Wu / Wd / WdT, device; empty: that matrix is time-invariant.  WdT_t stays empty under transpose_by_gather (Wd_t serves)
+    bool time_varying = false;
+    int solvers = 0;               // solvers created on this graph so far (the tables must be set before the first one)
+    DevBuf<float> Wu_t, Wd_t, WdT_t;
     int max_row_all = 0;
 
     OpDesc op_lu() const;

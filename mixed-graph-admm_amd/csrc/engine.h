@@ -18,6 +18,7 @@
 #include "tile_meta.h"
 #include "stream_keys.h"
 #include "stream_kernels.h"
+#include "stream_tv_kernels.h"
 #include "stream_plan.h"
 #include "lds_adapt.h"      // ldsadapt::Params, validate: set_adaptive_rho checks its arguments for either scalar type
 #include "lds_plan.h"
@@ -118,6 +119,7 @@ struct Engine : EngineBase {
         streamplan::Facts f;
         f.elem = (int)sizeof(S); f.T = T; f.N = N; f.spatial = g->mode == MGADMM_TEMPORAL_SPATIAL; f.reorder = g->reorder; f.q1 = g->q1;
         f.max_u = g->Wu.max_row; f.max_d = g->Wd.max_row; f.max_dt = g->WdT.max_row; f.avg_dt = g->WdT.avg_row_ceil;
+        f.time_varying = g->time_varying;
         return f;
     }
     // which matrix a spatial operator applies (the graph hands out its three device tables; transpose_by_gather: Ldr^T reads W_d's)
@@ -313,6 +315,12 @@ struct Engine : EngineBase {
         return {std::is_same<S, float>::value, q.path, q.cg_convergence, q.admm_convergence, q.check_stop, lds.ok, g->mode == MGADMM_TEMPORAL_BAND, N, T};
     }
     solvegate::SetState set_state() const { return {wt.sp_B, sg_B, wt.sch_rows, wt.sch_B, ad_on}; }
+    // time-varying weights (mgadmm_graph_set_time_weights) reach the row kernels only: the row sums of apply_op_Ln, the schedule
+    // of two_loops and the images of the per-sample graphs hold one slice
+    static int refuse_time_varying(const char* who) {
+        mg_set_error("%s: not on a graph with time-varying weights (mgadmm_graph_set_time_weights)", who);
+        return MGADMM_ERR_UNSUPPORTED;
+    }
     static int refused(const solvegate::Result& r) { if (r.rc != MGADMM_OK) mg_set_error("%s", r.msg.c_str()); return r.rc; }
 
     // The buffers sized by the iteration limits: max_cg_iter of `p`, and `rows` ADMM iterations of history (max_admm_iter; two_loops:
@@ -393,6 +401,7 @@ struct Engine : EngineBase {
     int set_sample_graphs(int n_sets, mgadmm_graph* const* graphs, const int32_t* set_of_sample, int B) override {
         MG_HIP(hipSetDevice(g->device));
         if (n_sets == 0) { sg_B = 0; return MGADMM_OK; }
+        if (g->time_varying) return refuse_time_varying("set_sample_graphs");
         MG_REQUIRE(n_sets >= 1 && graphs && set_of_sample, "set_sample_graphs: n_sets %d needs graphs and set_of_sample", n_sets);
         MG_REQUIRE(B >= 1 && B <= Bmax, "set_sample_graphs: batch %d outside [1, max_batch=%d]", B, Bmax);
         for (int b = 0; b < B; ++b)
@@ -401,6 +410,7 @@ struct Engine : EngineBase {
         for (int s = 0; s < n_sets; ++s) {
             const mgadmm_graph* q = graphs[s];
             MG_REQUIRE(q, "set_sample_graphs: graphs[%d] is null", s);
+            if (q->time_varying) return refuse_time_varying("set_sample_graphs");
             MG_REQUIRE(q->N == N && q->T == T, "set_sample_graphs: graphs[%d] has N = %d, T = %d, the solver's graph N = %d, T = %d", s, q->N, q->T, N, T);
             MG_REQUIRE(q->device == g->device, "set_sample_graphs: graphs[%d] lives on device %d, the solver on %d", s, q->device, g->device);
             MG_REQUIRE(q->mode == g->mode && q->transpose_by_gather == g->transpose_by_gather && q->q1 == g->q1 && q->skip == g->skip,
@@ -545,7 +555,9 @@ struct Engine : EngineBase {
         if (op.kind != OPK_SPATIAL) return 0.0;
         const streamplan::Mat m = mat_of(op);
         const int nnz = m == streamplan::M_WU ? g->Wu.nnz : (m == streamplan::M_WD ? g->Wd.nnz : g->WdT.nnz);
-        return (double)nnz * 8 + (double)(N + 1) * 4;
+        // (a per-slice table: the pattern once, the values of every slice the sweep reads)
+        const double vals = op.val_t ? (double)op.n_slices * op.slice_stride * 4 : (double)nnz * 4;
+        return (double)nnz * 4 + vals + (double)(N + 1) * 4;
     }
 
     // ---------------------------------------------------------------- launch helpers
@@ -623,6 +635,21 @@ struct Engine : EngineBase {
                     default: MG_TRY((launch_tile<VEC, Epi, 8>(c, tg, op, tmv, in, epi, live))); break;
                 }
                 cur_P = tg.P;
+            }
+        } else if (op.kind == OPK_SPATIAL && op.val_t != nullptr) {
+            // time-varying weights: the twin of k_rows that takes a row's weights from the slice of its time step (no instance
+            // key: stream_keys.h names the three time-invariant kernels)
+            if constexpr (is_elementwise<Epi>::value) {
+                mg_set_error("rows: element-wise epilogue launched with a spatial operator");
+                return MGADMM_ERR_INVALID;
+            } else {
+                if (op.self_w != nullptr) {
+                    mg_set_error("rows: no per-row self factor on time-varying weights");
+                    return MGADMM_ERR_UNSUPPORTED;
+                }
+                hipLaunchKernelGGL((k_rows_tv<S, VEC, Epi, GW>), dim3(q.grid), dim3(256), 0, st, q, op, op.rowptr, op.col, op.val_t,
+                                   in, epi, partials.get(), live);
+                cur_P = q.P;
             }
         } else {
             stream_keys.note(plan.key(c, Epi::ID, false));
@@ -853,6 +880,7 @@ struct Engine : EngineBase {
     int apply(int op, const void* x, void* y, int B, hipStream_t s) override {
         MG_TRY(check_B(B, "apply"));
         MG_REQUIRE(x && y, "apply: null pointer");
+        if (op == MGADMM_OP_LN && g->time_varying) return refuse_time_varying("apply(MGADMM_OP_LN)");
         st = s;
         Geom q = plan.make_geom(B);
         MG_TRY(ensure_partials(q));
@@ -1190,6 +1218,7 @@ struct Engine : EngineBase {
         MG_TRY(check_B(B, "two_loops"));
         MG_REQUIRE(y && x_out, "two_loops: null pointer");
         MG_REQUIRE(p.max_inner_iter >= 1, "two_loops: max_inner_iter must be >= 1 (got %d)", p.max_inner_iter);
+        if (g->time_varying) return refuse_time_varying("two_loops");
         st = s;
         const Geom q = plan.make_geom(B);
         MG_TRY(ensure_partials(q));

@@ -9,6 +9,7 @@
 #include <queue>
 
 #include "common.h"
+#include "tv_values.h"
 
 static thread_local char g_err[1024] = "";
 
@@ -21,25 +22,10 @@ void mg_set_error(const char* fmt, ...) {
 
 extern "C" const char* mgadmm_last_error(void) { return g_err; }
 // 0.2: mgadmm_params gained cg_convergence, max_inner_iter; 0.3: round-3 LDS path, more mgadmm_query_t codes (no struct change)
-extern "C" const char* mgadmm_version(void) { return "mgadmm 0.3.5 (gfx950)"; }
+extern "C" const char* mgadmm_version(void) { return "mgadmm 0.3.6 (gfx950)"; }
 
 int mg_transpose_csr(const HostCsr& A, HostCsr& At) {
-    const int n = A.n, nnz = A.nnz();
-    At.n = n;
-    At.rowptr.assign(n + 1, 0);
-    At.col.resize(nnz);
-    At.val.resize(nnz);
-    for (int e = 0; e < nnz; ++e) At.rowptr[A.col[e] + 1]++;
-    for (int i = 0; i < n; ++i) At.rowptr[i + 1] += At.rowptr[i];
-    std::vector<int> fill(At.rowptr.begin(), At.rowptr.end() - 1);
-    // rows visited in increasing order -> entries of every transposed row are sorted by source row:
-    // a fixed summation order, so results are bitwise repeatable (no atomics anywhere).
-    for (int i = 0; i < n; ++i)
-        for (int e = A.rowptr[i]; e < A.rowptr[i + 1]; ++e) {
-            int d = fill[A.col[e]]++;
-            At.col[d] = i;
-            At.val[d] = A.val[e];
-        }
+    transpose_csr(A, At);      // (host_csr.h: plain C++, shared with the per-slice tables of tv_values.h)
     return MGADMM_OK;
 }
 
@@ -230,6 +216,7 @@ OpDesc mgadmm_graph::op_lu() const {
     o.rowptr = Wu.rowptr.get(); o.col = Wu.col.get(); o.val = Wu.val.get();
     o.shift = 0;
     o.self_mode = SELF_ONE;
+    if (Wu_t) { o.val_t = Wu_t.get(); o.slice_stride = Wu.nnz; o.n_slices = T; }
     return o;
 }
 
@@ -240,6 +227,7 @@ OpDesc mgadmm_graph::op_ldr() const {
         o.kind = OPK_SPATIAL;
         o.rowptr = Wd.rowptr.get(); o.col = Wd.col.get(); o.val = Wd.val.get();
         o.shift = -1;
+        if (Wd_t) { o.val_t = Wd_t.get(); o.slice_stride = Wd.nnz; o.n_slices = T - 1; }
     } else {
         o.kind = OPK_BAND;
         o.band_w = band_w.get(); o.skip = skip; o.band_dir = -1;
@@ -255,6 +243,8 @@ OpDesc mgadmm_graph::op_ldrt() const {
         o.rowptr = WdT.rowptr.get(); o.col = WdT.col.get(); o.val = WdT.val.get();
         o.shift = +1;
         o.q1 = q1;
+        // (transpose_by_gather: WdT is a copy of Wd, pattern included, so W_d's table serves)
+        if (Wd_t) { o.val_t = transpose_by_gather ? Wd_t.get() : WdT_t.get(); o.slice_stride = WdT.nnz; o.n_slices = T - 1; }
     } else {
         o.kind = OPK_BAND;
         o.band_w = band_w.get(); o.skip = skip; o.band_dir = +1;
@@ -329,6 +319,47 @@ extern "C" int mgadmm_graph_create(const mgadmm_graph_desc* d, mgadmm_graph** ou
     if (rc != MGADMM_OK) { mgadmm_graph_destroy(g); return rc; }
     g->max_row_all = std::max(g->Wu.max_row, std::max(g->Wd.max_row, g->WdT.max_row));
     *out = g;
+    return MGADMM_OK;
+}
+
+// Time-varying weights: S value arrays on the caller's CSR patterns become the per-slice tables of the row kernel k_rows_tv
+// (tv_values.h: layout, slice rule, the transposes and the node order slice by slice).  The tables are staged in local owners:
+// whatever fails, the graph keeps what it had.
+extern "C" int mgadmm_graph_set_time_weights(mgadmm_graph* g, const float* u_val_t, int32_t n_u_slices, const float* d_val_t,
+                                             int32_t n_d_slices) {
+    MG_REQUIRE(g, "graph_set_time_weights: null graph");
+    if (g->mode == MGADMM_TEMPORAL_BAND) {
+        mg_set_error("graph_set_time_weights: a MGADMM_TEMPORAL_BAND graph has no W_d table (time-varying weights: kNN / physical graphs only)");
+        return MGADMM_ERR_UNSUPPORTED;
+    }
+    MG_REQUIRE(g->solvers == 0, "graph_set_time_weights: call it before a solver is created on the graph (%d so far)", g->solvers);
+    std::string err;
+    MG_REQUIRE(!u_val_t || tv::check_values("u_val_t", u_val_t, n_u_slices, g->T, g->hWu.nnz(), err), "graph_set_time_weights: %s", err.c_str());
+    MG_REQUIRE(!d_val_t || tv::check_values("d_val_t", d_val_t, n_d_slices, g->T - 1, g->hWd.nnz(), err), "graph_set_time_weights: %s", err.c_str());
+    if (!u_val_t && !d_val_t) return MGADMM_OK;
+    MG_HIP(hipSetDevice(g->device));
+    const std::vector<int>* perm = g->has_perm ? &g->perm : nullptr;
+    const std::vector<int>* iperm = g->has_perm ? &g->iperm : nullptr;
+    // `like`: the device CSR the table must lie on -- built by the same transpose and node order from the same pattern
+    auto stage = [&](const HostCsr& A, const float* vals, int S, bool transpose, const HostCsr& like_host, DevBuf<float>& out) -> int {
+        HostCsr pat, like;
+        std::vector<float> table;
+        MG_REQUIRE(tv::build_table(A, vals, S, transpose, perm, iperm, pat, table), "graph_set_time_weights: the slices do not share one structure");
+        if (perm) permute_csr(like_host, *perm, *iperm, like);
+        else like = like_host;
+        MG_REQUIRE(pat.rowptr == like.rowptr && pat.col == like.col, "graph_set_time_weights: the table does not lie on the graph's pattern");
+        MG_BUF(out.upload(table));
+        return MGADMM_OK;
+    };
+    DevBuf<float> u, d, dt;
+    if (u_val_t) MG_TRY(stage(g->hWu, u_val_t, g->T, false, g->hWu, u));
+    if (d_val_t) {
+        MG_TRY(stage(g->hWd, d_val_t, g->T - 1, false, g->hWd, d));
+        if (!g->transpose_by_gather) MG_TRY(stage(g->hWd, d_val_t, g->T - 1, true, g->hWdT, dt));
+    }
+    if (u_val_t) g->Wu_t = std::move(u);
+    if (d_val_t) { g->Wd_t = std::move(d); g->WdT_t = std::move(dt); }
+    g->time_varying = true;
     return MGADMM_OK;
 }
 

@@ -181,6 +181,7 @@ struct LdsEngine final : Engine<float> {
     int plan_lds() {
         if (hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess) { (void)hipGetLastError(); dev_cus = 0; }
         // which k_admm_lds instance, its geometry and the image of its tables: plain host code, lds_plan.h
+        if (g->time_varying) return MGADMM_OK;      // the images hold one slice of weights: no plan, MGADMM_Q_LDS_OK = 0, solve_gate.h refuses the rest
         std::vector<int> img;
         const ldsplan::Input in{T, N, g->mode == MGADMM_TEMPORAL_BAND, g->transpose_by_gather != 0, g->hWu, g->hWd, g->hWdT};
         lds_sw = ldsplan::Switches::from_env();

@@ -63,6 +63,7 @@ struct Facts {
     int q1 = 0;
     int max_u = 0, max_d = 0, max_dt = 0;   // the longest row of W_u, W_d, W_d^T
     int avg_dt = 0;               // ceil(mean row length) of W_d^T
+    bool time_varying = false;    // per-slice weights (mgadmm_graph_set_time_weights): the plain row kernels only, see tiled()
 };
 
 // The matrix of an operator application.  W_U .. W_DT in the order of the engine's tile tables
@@ -148,8 +149,10 @@ struct Planner {
         return q;
     }
 
-    // the LDS-tiled spatial kernel: cluster-ordered kNN / physical graphs
-    bool tiled() const { return sw.tile && f.reorder >= 2 && f.spatial; }
+    // the LDS-tiled spatial kernel: cluster-ordered kNN / physical graphs.  Not with time-varying weights: the tile tables of
+    // k_tile and k_cldr hold one slice, so such a graph gets the plan MGADMM_TILE=0 gives it (row kernels, two-pass Ldr^T Ldr,
+    // separate EpiPUpdate: cldr_wanted, fold1 and fold2 all follow from this)
+    bool tiled() const { return sw.tile && f.reorder >= 2 && f.spatial && !f.time_varying; }
     int tile_rows() const { return tiled() ? sw.tile_r : 0; }      // (MGADMM_Q_TILE_ROWS)
     // geometry of the LDS-tiled spatial kernel for the same column layout as `q`
     bool make_tile_geom(const Geom& q, TileGeom& tg) const {

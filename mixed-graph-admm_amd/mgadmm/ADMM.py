@@ -21,6 +21,7 @@ from . import _lib
 from . import utils as _u
 from .band_args import check_skips
 from .graph import Graph, expand_channels, tables_to_csr
+from .time_tables import table_slices
 from .solve_args import (ADAPTIVE_RHO_KEYS, GRAPH_PARAM_NAMES, SAMPLE_PARAM_NAMES, _check_adaptive_rho,  # noqa: F401
                          _check_graph_sets, _check_param_schedule, _check_sample_params, _float64,
                          geometric_ramp, parse_solve_args, solve_scope)
@@ -102,13 +103,23 @@ class ADMM_algorithm():
                       were solved alone (B samples = B independent B=1 runs, bit for bit).  ``solve`` then leaves the
                       iteration count of every sample in ``n_iters_per_sample``; the residual lists count a stopped
                       sample as standing still, ``delta_x_per_step`` stays empty.  LDS-resident float32 path only.
+      time_varying    False (default): ``u_ew`` / ``d_ew`` must be time-expanded repeats of one table, as the reference's
+                      constructor makes them.  True (kNN / physical graphs): a ``u_ew`` of shape (T, N, k) and a ``d_ew`` of
+                      shape (T-1, N, k+1) whose slices differ are accepted -- slice t of ``u_ew`` weighs the edges inside time
+                      step t, slice t of ``d_ew`` the edges from step t to t+1, as the reference's operators broadcast them
+                      (ADMM.py:147, 171, 200, 214).  Such an instance runs the streaming path with the plain row kernels;
+                      ``path='lds'``, ``sample_params``, ``graph_params`` / ``graph_sets``, ``two_loops`` and ``apply_op_Ln``
+                      are refused.  Tables whose slices are all equal still give the ordinary one-slice graph
+                      (``MGADMM_TV_KEEP=1``, a test hook, keeps the per-slice tables even then).
     """
     rho_history = rho_final = None      # of the last solve(adaptive_rho=...)
 
     def __init__(self, graph_info, ADMM_info, use_kNN=False, k=4, u_sigma=None, d_sigma=None, expand_time_dim=True,
                  ablation='None', t_in=12, T=24, use_line_graph=False, skip_connection=1, *, device=None,
                  compute_dtype=torch.float32, bug_compat=True, tables=None, reorder='auto', record_cg_coeffs='auto',
-                 path='auto', graph_backend='auto', cg_convergence='per_sample', admm_convergence='whole_batch'):
+                 path='auto', graph_backend='auto', cg_convergence='per_sample', admm_convergence='whole_batch',
+                 time_varying=False):
+        self.time_varying = bool(time_varying)
         if cg_convergence not in ('per_sample', 'batch_max'):
             raise ValueError(f"cg_convergence must be 'per_sample' or 'batch_max', got {cg_convergence!r}")
         self.cg_convergence = cg_convergence
@@ -246,7 +257,7 @@ class ADMM_algorithm():
         # identity AND in-place version of every table: `blk.u_ew = ...` and `blk.u_ew.mul_(2)` both rebuild the device CSR
         tv = lambda t: (id(t), getattr(t, "_version", 0), tuple(t.shape))
         return (tv(self.connect_list), tv(self.u_ew), tv(self.d_ew), self.use_line_graph, self.skip_connection,
-                self.use_kNN, self.bug_compat, self.T)
+                self.use_kNN, self.bug_compat, self.T, self.time_varying)
 
     @staticmethod
     def _time_invariant(tab, name):
@@ -274,6 +285,14 @@ class ADMM_algorithm():
 
     def _make_graph(self, Cn, u_ew, d_ew):
         """A device graph of this instance's topology, mode and node order with the weight tables ``u_ew`` / ``d_ew``."""
+        u_t = d_t = None
+        if self.time_varying and not self.use_line_graph:
+            u_t, d_t = table_slices(u_ew, "u_ew", self.T), table_slices(d_ew, "d_ew", self.T - 1)
+            # the graph is created on slice 0; the per-slice values follow, on the same CSR pattern (connect_list alone decides it)
+            u_val_t = u_t and np.stack([expand_channels(tables_to_csr(self.connect_list, w, 1), Cn)[2] for w in u_t])
+            d_val_t = d_t and np.stack([expand_channels(tables_to_csr(self.connect_list, w, 0), Cn)[2] for w in d_t])
+            u_ew = u_t[0] if u_t else u_ew
+            d_ew = d_t[0] if d_t else d_ew
         u_ew = self._time_invariant(u_ew, "u_ew")
         u_csr = expand_channels(tables_to_csr(self.connect_list, u_ew, 1), Cn)
         N = self.n_nodes * Cn
@@ -292,7 +311,8 @@ class ADMM_algorithm():
             d_ew = self._time_invariant(d_ew, "d_ew")
             d_csr = expand_channels(tables_to_csr(self.connect_list, d_ew, 0), Cn)
             gph = Graph(N, self.T, u_csr, d_csr, transpose_by_gather=not self.use_kNN,
-                        q1_identity_t0=self.bug_compat, reorder=reorder, device=dev.index or 0)
+                        q1_identity_t0=self.bug_compat, reorder=reorder, device=dev.index or 0,
+                        u_val_t=u_val_t if u_t else None, d_val_t=d_val_t if d_t else None)
         return gph
 
     def _params(self, dtype, B):

@@ -99,6 +99,7 @@ SYMBOLS = {
     "mgadmm_graph_transpose_nnz": (C.c_int, [_vp, _i32p]),
     "mgadmm_graph_get_transpose": (C.c_int, [_vp, _i32p, _i32p, _f32p]),
     "mgadmm_graph_get_perm": (C.c_int, [_vp, _i32p]),
+    "mgadmm_graph_set_time_weights": (C.c_int, [_vp, _f32p, C.c_int32, _f32p, C.c_int32]),
     "mgadmm_solver_create": (C.c_int, [_vp, C.POINTER(Params), C.c_int32, C.POINTER(_vp)]),
     "mgadmm_solver_destroy": (C.c_int, [_vp]),
     "mgadmm_solver_set_params": (C.c_int, [_vp, C.POINTER(Params)]),

@@ -57,7 +57,7 @@ class Graph:
     """Owns one mgadmm_graph handle (device-resident CSR of W_u, W_d, W_d^T)."""
 
     def __init__(self, n_nodes, T, u_csr, d_csr=None, *, band_w=None, skip=1, transpose_by_gather=False,
-                 q1_identity_t0=True, reorder=False, device=0):
+                 q1_identity_t0=True, reorder=False, device=0, u_val_t=None, d_val_t=None):
         self.n_nodes, self.T, self.device = int(n_nodes), int(T), int(device)
         self._keep = []
         d = _lib.GraphDesc()
@@ -84,6 +84,21 @@ class Graph:
         _lib.check(_lib.lib.mgadmm_graph_create(C.byref(d), C.byref(h)))
         self.handle = h
         self.spatial = d_csr is not None
+        # time-varying weights: the values of every time slice on the patterns above, [T][nnz] for W_u, [T-1][nnz] for W_d
+        self.time_varying = u_val_t is not None or d_val_t is not None
+        if self.time_varying:
+            tabs = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (u_val_t, d_val_t)]
+            for nm, a, pat in zip(("u_val_t", "d_val_t"), tabs, (u_csr, d_csr)):
+                if a is not None and (pat is None or a.ndim != 2 or a.shape[1] != len(pat[2])):
+                    self.close()
+                    raise ValueError(f"{nm} must have shape (slices, {0 if pat is None else len(pat[2])}), the values of every "
+                                     f"slice on the graph's CSR pattern, got {a.shape}")
+            args = [x for a in tabs for x in ((None, 0) if a is None else (_ptr(a, C.c_float), a.shape[0]))]
+            try:
+                _lib.check(_lib.lib.mgadmm_graph_set_time_weights(self.handle, *args))
+            except _lib.MgadmmError:
+                self.close()
+                raise
 
     def transpose_csr(self):
         nnz = C.c_int32()
